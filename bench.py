@@ -13,8 +13,8 @@ so every utterance runs a forced number of loop steps):
            S=45, H=264 (P=132 prompts), 5.3 s reference.  A step = one utterance
            of a stream of them (a paragraph split into sentences): each one's
            vocoder runs on --vocoder-cus CUs of its own (default 64) beside the
-           next one's T2S on the other CUs (gsv_vits_decode_async); the line's
-           "sequential" object times one utterance alone on every CU
+           next one's T2S on the other CUs (gsv_vits_decode_async); with --full
+           the line's "sequential" object times one utterance alone on every CU
            (--vocoder-cus 0 makes that the headline mode).
   batch64  configs[2]: 64 mixed-length JP sentences (S~U[30,60], G~U[50,110]),
            top-k 5 sampled, ONE ragged batched decode + the vocoder per
@@ -30,13 +30,20 @@ Inputs are resident in HBM before the timed region.  Multi-GPU: one process per
 GPU (torchrun), independent replicas, no collective on the data path; the
 barrier and the max-over-ranks time use a gloo (host) group -- no RCCL.
 
-The single workload's line also carries "concurrent_streams": the same stream run by two
-child ranks sharing the GPU (each decoding on 96 CUs of its own, the vocoder CUs shared;
---streams-per-gpu), the GPU's rate under concurrent single-sentence requests.  The batched
-workloads pipeline each batch's vocoder beside the next batch's T2S (--pipeline 0: one batch
-at a time).
+A plain run sets up, warms up, times the K steps and prints the result line (rate, rtf,
+ms_per_step, the phase times of the timed steps).  --full adds, after the timed steps, the
+measurements that take runs of their own: "roofline" (+ the achievable-HBM copy) and
+"roofline_utterance", "sequential", "cpu_baseline" (--no-cpu-baseline skips it) and, on the
+single workload, "concurrent_streams": the same stream run by two child ranks sharing the
+GPU (each decoding on 96 CUs of its own, the vocoder CUs shared; --streams-per-gpu), the
+GPU's rate under concurrent single-sentence requests.  The batched workloads pipeline each
+batch's vocoder beside the next batch's T2S (--pipeline 0: one batch at a time).
+
+--dump-outputs DIR writes what the last timed step returned (semantic tokens and waveforms,
+float32 .npy; dump_outputs below).  The inputs are seeded, the same from run to run.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload single|batch64|mixed100]
+                       [--full] [--dump-outputs DIR]
                        [--vocoder-cus K] [--concurrent-streams S] [--pipeline 0|1]
                        [--vits-lanes L] [--no-cpu-baseline]
 """
@@ -143,6 +150,7 @@ class Runner:
             self.finish()                                   # the previous utterance's vocoder
             self.pending = eng.vits_decode_async(dict(text_seq=utt(i)[1], pred_semantic=sems[0],
                                                       noise_seed=self.seed, **cond))
+            self.last_wavs = [self.pending]
         self.finish()
         return sems, 1280 * int(sems[0].size)
 
@@ -183,6 +191,7 @@ class Runner:
             wavs = self.eng.vits_decode_batch([dict(text_seq=t, pred_semantic=sem, noise_seed=self.seed + i, **cond)
                                                for i, (t, sem) in enumerate(zip(self.d_txt, sems))])
         n = sum(int(w.numel()) for w in wavs)
+        self.last_wavs = wavs
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         self.phase["t2s"] += t1 - t0
@@ -199,6 +208,7 @@ class Runner:
         bounds = [n * j // nb for j in range(nb + 1)]
         cond = dict(ge=self.ge_v2) if self.ge is None else dict(ge=self.ge, ge_advanced=self.ge_adv)
         sems_all, n_samples = [], 0
+        self.last_wavs = []                    # this pass's audio tensors, valid after drain()
         for j in range(nb):
             lo, hi = bounds[j], bounds[j + 1]
             t0 = time.perf_counter()
@@ -219,6 +229,7 @@ class Runner:
             self.phase["t2s"] += t1 - t0
             self.phase["vits"] += t2 - t1      # the host's wait for the previous vocoder (not hidden)
             sems_all += sems
+            self.last_wavs += wavs
             n_samples += sum(int(w.numel()) for w in wavs)
         return sems_all, n_samples
 
@@ -226,6 +237,34 @@ class Runner:
         if getattr(self, "batch_pending", False):
             self.eng.vits_batch_wait()
             self.batch_pending = False
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, sems, wavs, rank=None):
+    """--dump-outputs: what the last timed step returned to its caller, as float32 .npy files
+    under `path`: the semantic tokens and the waveforms of its utterances, each concatenated
+    in utterance order, with the per-utterance lengths beside them.  A waveform set past the
+    size budget is stored as a fixed seeded sample (its indices into the concatenation in
+    waveform_index.npy, float64).  Ranks of a multi-GPU run write <name>.rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    sfx = "" if rank is None else f".rank{rank}"
+    save = lambda name, a: np.save(os.path.join(path, f"{name}{sfx}.npy"), a)
+    tok = np.concatenate([np.asarray(s).reshape(-1) for s in sems]).astype(np.float32)
+    wav = np.concatenate([w.detach().float().cpu().numpy().reshape(-1) for w in wavs])
+    save("semantic_tokens", tok)
+    save("semantic_lengths", np.asarray([np.asarray(s).size for s in sems], np.float32))
+    save("waveform_lengths", np.asarray([int(w.numel()) for w in wavs], np.float32))
+    room = DUMP_MAX_BYTES - tok.nbytes - 8 * len(sems) - (1 << 16)   # the other files and the .npy headers
+    index = os.path.join(path, f"waveform_index{sfx}.npy")
+    if wav.size * 4 > room:
+        idx = np.sort(np.random.default_rng(0x5EED).choice(wav.size, size=room // 12, replace=False))
+        np.save(index, idx.astype(np.float64))       # 4 B sample + 8 B index each
+        wav = wav[idx]
+    elif os.path.exists(index):                      # an earlier, sampled dump's: not this one's
+        os.remove(index)
+    save("waveform", wav.astype(np.float32))
 
 
 def concurrent_streams(args):
@@ -350,7 +389,12 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", choices=("single", "batch64", "mixed100"), default="single")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary measurements (roofline figures and the "
+                         "achievable-HBM copy, one utterance alone, the CPU baseline, concurrent streams)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (semantic tokens, waveforms) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--vits-lanes", type=int, default=0,
                     help="batched workloads: concurrent vocoder streams (0 = the engine default)")
     ap.add_argument("--vocoder-cus", type=int, default=64,
@@ -363,7 +407,7 @@ def main():
                     help="single workload under torchrun: S ranks share one GPU, each decoding on "
                          "--decode-cus CUs of its own (offset rank %% S x decode-cus) beside the shared vocoder CUs")
     ap.add_argument("--concurrent-streams", type=int, default=2,
-                    help="single workload, N=1: also time this many sentence streams sharing the GPU "
+                    help="single workload, N=1, --full: also time this many sentence streams sharing the GPU "
                          "(child ranks, --streams-per-gpu) and report them beside the headline (0/1 = off)")
     ap.add_argument("--pipeline", type=int, default=1,
                     help="batched workloads: 1 = each batch's vocoder beside the next batch's T2S, "
@@ -480,12 +524,14 @@ def main():
     if dist is not None:
         dist.barrier()
     dt, per_rank = over_ranks(dist, dt, args.steps * len(items))   # this rank's utterances
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sems, run.last_wavs, rank if world > 1 else None)
 
     R_, H_ = wl.reference.ref_seq.shape[1], wl.reference.ssl.shape[2]
     n0s = [R_ + it.text_seq.shape[1] + H_ // 2 for it in items]
-    roof = persist_roofline(run.eng, n0=n0s[0], steps=items[0].force_steps, B=1) if timed_single else None
+    roof = persist_roofline(run.eng, n0=n0s[0], steps=items[0].force_steps, B=1) if timed_single and args.full else None
     seq = None
-    if overlap and rank == 0 and world == 1:
+    if args.full and overlap and rank == 0 and world == 1:
         # one utterance alone (no overlap, every CU): the single-request latency
         run.eng.set_vocoder_cus(0)
         run.step()
@@ -546,7 +592,8 @@ def main():
             roof["achievable_hbm"] = {"value": ach, "unit": "GB/s", "frac": roof["achieved"] / ach,
                                       "how": "non-temporal grid-stride copy of 1 GiB x 10 on this GPU "
                                              "(gsv_debug_hbm_copy), read + write bytes"}
-        out["roofline"] = roof
+        if args.full:
+            out["roofline"] = roof
         if seq is not None:
             out["sequential"] = {"utt_s": 1.0 / seq, "ms_per_utt": seq * 1e3, "x_realtime": audio_s / seq,
                                  "note": "one utterance at a time on every CU (single-request latency)"}
@@ -554,9 +601,10 @@ def main():
             pm = np.mean(np.asarray(phase_ms), axis=0)
             out["phase_ms"] = {"encode": float(pm[0]), "prefill": float(pm[1]), "decode": float(pm[2]),
                                "vits": float(pm[3])}
-            out["roofline_utterance"] = composite_roofline(
-                ms_per_step, n0s, [it.force_steps], tokens, wl.version,
-                {"decode": float(pm[2]), "prefill": float(pm[1]), "vits": float(pm[3])})
+            if args.full:
+                out["roofline_utterance"] = composite_roofline(
+                    ms_per_step, n0s, [it.force_steps], tokens, wl.version,
+                    {"decode": float(pm[2]), "prefill": float(pm[1]), "vits": float(pm[3])})
     else:
         out["config"] = {"workload": wl.name + (" (top-k %d sampled)" % wl.top_k if not wl.greedy else " (greedy)"),
                          "version": wl.version, "sentences": len(wl.items), "sentences_this_rank": len(items),
@@ -569,9 +617,10 @@ def main():
             out["config"]["shard"] = args.shard
         ph = {k: v / args.steps * 1e3 for k, v in run.phase.items()}
         out["phase_ms"] = ph
-        out["roofline_utterance"] = composite_roofline(ms_per_step, n0s, [it.force_steps for it in items], tokens,
-                                                       wl.version)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "single":
+        if args.full:
+            out["roofline_utterance"] = composite_roofline(ms_per_step, n0s, [it.force_steps for it in items],
+                                                           tokens, wl.version)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "single":
         # every CPU this job is allotted: the GPU box gives one GPU's job 16 host CPUs
         # (OMP_NUM_THREADS=16 there) although the machine shows more; here: all 8
         threads = min(int(os.environ.get("OMP_NUM_THREADS") or 10 ** 6), len(os.sched_getaffinity(0)))
@@ -587,7 +636,8 @@ def main():
                                "sample": f"1 full utterance ({cs} samples) of the same workload, "
                                          f"oracle/restate.py torch-fp32 on {model}",
                                "rtf": cdt / (cs / SR)}
-    if (rank == 0 and world == 1 and overlap and args.concurrent_streams > 1 and args.streams_per_gpu == 1):
+    if (args.full and rank == 0 and world == 1 and overlap and args.concurrent_streams > 1
+            and args.streams_per_gpu == 1):
         out["concurrent_streams"] = concurrent_streams(args)
     if rank == 0:
         print(json.dumps(out), flush=True)

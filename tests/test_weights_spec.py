@@ -1,6 +1,7 @@
 """CPU: weight tables vs the reference templates, and the Genie on-disk format
 (fp16 bins addressed through the relinked graph's fp32 offsets,
 g/ModelManager.py:59-114) read back through genie_tts_amd.weights."""
+import json
 import os
 
 import numpy as np
@@ -9,10 +10,10 @@ import pytest
 from genie_tts_amd import synth, weights as W
 from tests.onnx_writer import model
 
-REF = "/root/reference/src/genie_tts/Data"
+# the template graphs' initializer tables (name -> shape), recorded by golden/make_weight_templates.py
+TEMPLATES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "weight_templates.json")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference templates not present")
 @pytest.mark.parametrize("rel,spec", [
     ("v2/Models/t2s_first_stage_decoder_fp32.onnx", W.t2s_spec),
     ("v2/Models/t2s_stage_decoder_fp32.onnx", W.t2s_spec),
@@ -22,12 +23,12 @@ REF = "/root/reference/src/genie_tts/Data"
     ("v2ProPlus/Models/prompt_encoder_fp32.onnx", W.prompt_encoder_spec),
 ])
 def test_spec_matches_template(rel, spec):
-    from genie_tts_amd.onnx_table import read_initializer_table
-    table = read_initializer_table(os.path.join(REF, rel))
+    with open(TEMPLATES) as f:
+        table = json.load(f)[rel]
     s = spec()
     assert set(table) == set(s)
     for name, shape in s.items():
-        assert tuple(table[name][0]) == tuple(shape), name
+        assert tuple(table[name]) == tuple(shape), name
 
 
 def test_param_counts():

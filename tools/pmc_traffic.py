@@ -14,8 +14,9 @@ from genie_tts_amd.probe import kernel_source_sha  # noqa: E402
 
 tag = sys.argv[1]
 sub = sys.argv[2] if len(sys.argv) > 2 else "k_decode_persist"
-f = json.load(open(f"gpurun_out/{tag}_pmc_FETCH_SIZE.json"))["kernels"]
-w = json.load(open(f"gpurun_out/{tag}_pmc_WRITE_SIZE.json"))["kernels"]
+out_dir = os.environ.get("GENIE_ROUND_OUT", "round_out")     # where tools/gpu_round.sh wrote them
+f = json.load(open(f"{out_dir}/{tag}_pmc_FETCH_SIZE.json"))["kernels"]
+w = json.load(open(f"{out_dir}/{tag}_pmc_WRITE_SIZE.json"))["kernels"]
 out = {}
 for k, v in f.items():
     if sub not in k:

@@ -13,7 +13,7 @@ steps, warmup = 20, 3
 
 
 def run(extra):
-    cmd = [sys.executable, "bench.py", "--workload", "mixed100", "--no-cpu-baseline", "--steps", str(steps),
+    cmd = [sys.executable, "bench.py", "--workload", "mixed100", "--steps", str(steps),
            "--warmup", str(warmup)] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     if r.returncode != 0:
