@@ -309,7 +309,6 @@ int gsv_engine::finalize_t2s() {
         if (s->data.size() == 256) div = s->data;
     pe_max = 4096;
     if (const char* e = std::getenv("GENIE_FFN_SLICES")) ffn_slices = std::atoi(e) == 32 ? 32 : 64;
-    if (const char* e = std::getenv("GENIE_DECODE_FUSE")) fuse_qkv = std::atoi(e) == 2;
     if (const char* e = std::getenv("GENIE_ACC")) use_acc = std::atoi(e) != 0;
     if (const char* e = std::getenv("GENIE_PERSIST")) use_persist = std::atoi(e) != 0;
     if (const char* e = std::getenv("GENIE_PERSIST1")) use_persist1 = std::atoi(e) != 0;
@@ -606,8 +605,7 @@ int gsv_engine::prefill_slot(int b, const float* x, int L, const int64_t* pr, in
         at.q = pQ; at.ldq = 512; at.k = kcache[l] + b * sstride; at.v = vcache[l] + b * sstride;
         at.seq_stride = sstride; at.tmax = tmax; at.row_len = prow_len; at.out = pO; at.ldo = 512;
         at.rows = N0; at.scale = qk_scale;
-        if (use_attn_mf32 && prefill_mf32_on()) attn_rows_mf32_seq(at, st);   // the f32 MFMA, k_attn_flash's arithmetic
-        else attn_rows(at, st);
+        attn_rows(at, st);
         // out-proj and FFN2 have 32 output tiles: split K over 4 / 8 blocks into slabs,
         // reduced in fixed order (+ bias + residual) by the LayerNorm that follows
         const bool slabs = gemm_slabs_supported(512, 512, 512) && gemm_slabs_supported(2048, 2048, 2048);
@@ -727,22 +725,12 @@ int gsv_engine::prefill_packed(int B, const gsv_utt* utts, const gsv_sampler* sp
     const int R = off[B];
     if (int e = ensure_packed(R, B)) return e;
     // host row tables: sequence, position, visible keys; last row of each sequence
-    // tiles of <= TR rows of one sequence for the attention: 128 on the MFMA kernel, else
-    // 16 for the LDS-staged f32 kernels
-    const bool mfma_attn = attn_mfma_on();
-    // the row-per-lane f32 kernel (k_attn_rowlane; GENIE_PACKED_ROWLANE=0: k_attn_flash
-    // over 16-row tiles, the same results)
-    static const bool rowlane_opt = [] { const char* e = std::getenv("GENIE_PACKED_ROWLANE"); return !(e && std::atoi(e) == 0); }();
-    // the same arithmetic on the f32 MFMA (k_attn_mf32; GENIE_PACKED_MF32=0: k_attn_rowlane)
-    static const bool mf32_opt = [] { const char* e = std::getenv("GENIE_PACKED_MF32"); return !(e && std::atoi(e) == 0); }();
-    const bool mf32 = !mfma_attn && mf32_opt && use_attn_mf32;
-    const bool rowlane = !mfma_attn && !mf32 && rowlane_opt;
-    const int TR = mfma_attn ? 128 : mf32 ? 32 * MF32_NW : rowlane ? 64 * ROWLANE_NW : 16;
-    int ntiles = 0, maxn0 = 0;
-    for (int b = 0; b < B; ++b) {
-        ntiles += (off[b + 1] - off[b] + TR - 1) / TR;
-        maxn0 = std::max(maxn0, off[b + 1] - off[b]);
-    }
+    // tiles of <= TR rows of one sequence for the attention: the f32 MFMA kernel (k_attn_mf32), or
+    // with option attn_mf32 off the row-per-lane kernel (k_attn_rowlane); both run k_attn_flash's
+    // per-row arithmetic, so the results are the same
+    const int TR = use_attn_mf32 ? 32 * MF32_NW : 64 * ROWLANE_NW;
+    int ntiles = 0;
+    for (int b = 0; b < B; ++b) ntiles += (off[b + 1] - off[b] + TR - 1) / TR;
     pk_host.resize((size_t)3 * R + B + 3 * (size_t)ntiles);
     int* hs = pk_host.data();
     int* hp = hs + R;
@@ -777,13 +765,6 @@ int gsv_engine::prefill_packed(int B, const gsv_utt* utts, const gsv_sampler* sp
         pk_tile_cap = cap;
     }
     hipMemcpyAsync(pk_tiles, htile, (size_t)3 * ntiles * 4, hipMemcpyHostToDevice, st);
-    // the LDS-staged tile kernel measured slower here (prefill 62.5 vs 45.4 ms at B=64):
-    // kept behind GENIE_PACKED_TILE for A/B
-    static const bool tile_opt = [] { const char* e = std::getenv("GENIE_PACKED_TILE"); return e && std::atoi(e); }();
-    const bool tiled = !mfma_attn && !mf32 && !rowlane && tile_opt && maxn0 <= ATTN_TILE_MAXK;
-    // the online-softmax kernel over the same tiles (GENIE_PACKED_FLASH=0: the per-row kernel)
-    static const bool flash_opt = [] { const char* e = std::getenv("GENIE_PACKED_FLASH"); return !(e && std::atoi(e) == 0); }();
-    const bool flash_tiles = flash_opt;
     const int* row_seq = pk_rowinfo;
     const int* row_pos = pk_rowinfo + R;
     const int* row_len = pk_rowinfo + 2 * R;
@@ -824,29 +805,10 @@ int gsv_engine::prefill_packed(int B, const gsv_utt* utts, const gsv_sampler* sp
         at.q = pk_Q; at.ldq = 512; at.k = kcache[l]; at.v = vcache[l];
         at.seq_stride = sstride; at.tmax = tmax; at.row_len = row_len; at.row_seq = row_seq;
         at.out = pk_O; at.ldo = 512; at.rows = R; at.scale = qk_scale;
-        if (mfma_attn) {   // 128-row tiles of one sequence on the split-fp16 MFMA
-            at.tiles = pk_tiles;
-            at.ntiles = ntiles;
-            attn_rows_mfma(at, 128, st);
-        } else if (mf32) {   // tiles of 32 MF32_NW rows on the f32 MFMA
-            at.tiles = pk_tiles;
-            at.ntiles = ntiles;
-            attn_rows_mf32(at, st);
-        } else if (rowlane) {   // tiles of 64 ROWLANE_NW rows, one row per lane
-            at.tiles = pk_tiles;
-            at.ntiles = ntiles;
-            attn_rows_rowlane(at, st);
-        } else if (tiled) {
-            at.tiles = pk_tiles;
-            at.ntiles = ntiles;
-            attn_rows_tiled(at, st);
-        } else if (flash_tiles) {   // 16-row tiles of one sequence, K/V staged once per tile
-            at.tiles = pk_tiles;
-            at.ntiles = ntiles;
-            attn_rows_flash_tiled(at, st);
-        } else {
-            attn_rows(at, st);
-        }
+        at.tiles = pk_tiles;
+        at.ntiles = ntiles;
+        if (use_attn_mf32) attn_rows_mf32(at, st);
+        else attn_rows_rowlane(at, st);
         GemmArgs go{};
         go.M = R; go.N = 512; go.K = 512; go.A = pk_O; go.lda = 512;
         go.W = W.w_out; go.ldw = 512; go.w_f16 = 1; go.bias = W.b_out;
@@ -917,57 +879,41 @@ SampleArgs gsv_engine::sampler_args(const gsv_sampler* sp, int B) {
 void gsv_engine::decode_step(int B, const gsv_sampler* sp, float* logits_out, hipStream_t st) {
     const long sstride = (long)16 * tmax * 32;
     // fixed-point hand-off slices of layer l (fused path): FFN output, attention output
-    const bool acc = use_acc && !fuse_qkv && B <= 8 && tmax <= 1024;
+    const bool acc = use_acc && B <= 8 && tmax <= 1024;
     auto accF = [&](int l) { return acc ? acc64 + (long)(2 * l) * 512 : nullptr; };
     auto accA = [&](int l) { return acc ? acc64 + (long)(2 * l + 1) * 512 : nullptr; };
     decode_embed(B, y, tmax, ny, emb_audio, alpha_audio, pe_tab, h, done, st);
     if (B <= 8 && tmax <= 1024) {
-        // fused path: 2 launches per layer (QKV+attention+out-proj | FFN1+FFN2)
+        // fused path: 3 launches per layer (QKV GEMV | attention + out-proj | FFN1 + FFN2)
         for (int l = 0; l < 24; ++l) {
             const T2SLayerW& W = layers[l];
-            if (fuse_qkv) {
-                QkvAttnArgs qa{};
-                qa.B = B;
-                if (l == 0) {
-                    qa.src = h;
-                } else {
-                    qa.part = ffn_part; qa.n_part = ffn_slices; qa.part_stride = (long)B * 512;
-                    qa.part_bias = layers[l - 1].b2; qa.part_res = h1;
-                    qa.ln_g = layers[l - 1].n2w; qa.ln_b = layers[l - 1].n2b; qa.ln_out = h;
-                }
-                qa.W_in = W.w_in; qa.b_in = W.b_in; qa.k = kcache[l]; qa.v = vcache[l];
-                qa.seq_stride = sstride; qa.tmax = tmax; qa.kvlen = kvlen; qa.done = done;
-                qa.scale = qk_scale; qa.WoT = W.woT; qa.attn_part = attn_part;
-                qkv_attn_outproj(qa, st);
+            GemvArgs a{};
+            a.B = B; a.N = 1536; a.K = 512;
+            if (l == 0) {
+                a.src = h; a.lds = 512;
             } else {
-                GemvArgs a{};
-                a.B = B; a.N = 1536; a.K = 512;
-                if (l == 0) {
-                    a.src = h; a.lds = 512;
-                } else {
-                    a.part = ffn_part; a.n_part = ffn_slices; a.part_stride = (long)B * 512;
-                    a.part_bias = layers[l - 1].b2; a.part_res = h1;
-                    a.ln_g = layers[l - 1].n2w; a.ln_b = layers[l - 1].n2b; a.ln_out = h;
-                }
-                a.W = W.w_in; a.bias = W.b_in; a.C = q; a.ldc = 512; a.mode = EPI_QKV;
-                a.kv.k = kcache[l]; a.kv.v = vcache[l]; a.kv.tmax = tmax; a.kv.row_pos = kvlen;
-                a.kv.seq_stride = sstride; a.kv.row_skip = done;
-                if (l > 0) { a.acc_in = accF(l - 1); a.acc_bstride = ACC_SEQ; }
-                if (l == probe_layer) a.trace = ktrace;
-                gemv_f16(a, st);
-                AttnOutArgs ao{};
-                ao.B = B; ao.q = q; ao.k = kcache[l]; ao.v = vcache[l]; ao.seq_stride = sstride;
-                ao.tmax = tmax; ao.kvlen = kvlen; ao.done = done; ao.scale = qk_scale;
-                ao.WoT = W.woT; ao.part = attn_part;
-                ao.acc_out = accA(l); ao.acc_bstride = ACC_SEQ;
-                if (l == probe_layer && ktrace) ao.trace = ktrace + 256 * 8;
-                attn_outproj(ao, st);
+                a.part = ffn_part; a.n_part = ffn_slices; a.part_stride = (long)B * 512;
+                a.part_bias = layers[l - 1].b2; a.part_res = h1;
+                a.ln_g = layers[l - 1].n2w; a.ln_b = layers[l - 1].n2b; a.ln_out = h;
             }
+            a.W = W.w_in; a.bias = W.b_in; a.C = q; a.ldc = 512; a.mode = EPI_QKV;
+            a.kv.k = kcache[l]; a.kv.v = vcache[l]; a.kv.tmax = tmax; a.kv.row_pos = kvlen;
+            a.kv.seq_stride = sstride; a.kv.row_skip = done;
+            if (l > 0) { a.acc_in = accF(l - 1); a.acc_bstride = ACC_SEQ; }
+            if (l == probe_layer) a.trace = ktrace;
+            gemv_f16(a, st);
+            AttnOutArgs ao{};
+            ao.B = B; ao.q = q; ao.k = kcache[l]; ao.v = vcache[l]; ao.seq_stride = sstride;
+            ao.tmax = tmax; ao.kvlen = kvlen; ao.done = done; ao.scale = qk_scale;
+            ao.WoT = W.woT; ao.part = attn_part;
+            ao.acc_out = accA(l); ao.acc_bstride = ACC_SEQ;
+            if (l == probe_layer && ktrace) ao.trace = ktrace + 256 * 8;
+            attn_outproj(ao, st);
             FfnArgs fa{};
             fa.B = B; fa.nslices = ffn_slices; fa.h = h; fa.bo = W.b_out; fa.attn_part = attn_part;
             fa.ln_g = W.n1w; fa.ln_b = W.n1b; fa.h1 = h1;
             fa.W1 = W.w1; fa.b1 = W.b1; fa.W2T = W.w2T; fa.part = ffn_part;
-            if (!fuse_qkv) { fa.acc_attn = accA(l); fa.acc_out = accF(l); fa.acc_bstride = ACC_SEQ; }
+            fa.acc_attn = accA(l); fa.acc_out = accF(l); fa.acc_bstride = ACC_SEQ;
             if (l == probe_layer && ktrace) fa.trace = ktrace + 2 * 256 * 8;
             if (probe_now && l == probe_layer) ffn_fused(fa, st, kev[0], kev[1]);
             else ffn_fused(fa, st);
@@ -2050,8 +1996,6 @@ extern "C" int gsv_set_option(gsv_engine* eng, const char* name, int value) {
         eng->vits_lanes = value;
     } else if (n == "gemm_presplit") {   // the packed prefill's large GEMMs on pre-split A (same results)
         eng->use_presplit = value != 0;
-    } else if (n == "convh_persist") {
-        eng->convh_persist = value != 0;
     } else if (n == "convh_ws") {   // 0 off, 1 every batched generator pass, 2 (default) a batch vocoded alone
         eng->convh_ws = std::max(0, std::min(2, value));
     } else if (n == "vits_fork") {

@@ -128,7 +128,6 @@ struct gsv_engine {
     float *f = nullptr, *logits = nullptr;
     float *attn_part = nullptr, *ffn_part = nullptr;
     int ffn_slices = 64;
-    bool fuse_qkv = false;  // 3 launches/layer measured faster than 2 (GENIE_DECODE_FUSE=2 to A/B)
     float *pH = nullptr, *pQ = nullptr, *pO = nullptr, *pS = nullptr, *pH1 = nullptr, *pF = nullptr;
     int* prow_len = nullptr;
     int64_t* prompts_buf = nullptr;
@@ -194,7 +193,6 @@ struct gsv_engine {
     int convh_ws = 2;
     bool vb_alone = false;             // the batch being issued is a synchronous gsv_vits_decode_batch
     bool mrf_fused = true;             // option "mrf_fused": the C <= 32 stages' conv pairs as one kernel
-    bool convh_persist = false;        // option "convh_persist": large split-fp16 convs as a persistent tile loop
     int stream_cus(hipStream_t st) const;
     int* vovf = nullptr;               // f16-split conv overflow flag (device)
     int* vovf_host = nullptr;          // pinned copy

@@ -118,15 +118,10 @@ struct AttnArgs {
     int rows;
     float scale;                       // sqrt(1/sqrt(32)) applied to q and k separately
     const uint8_t* row_skip;
-    const int* tiles;                  // packed prefill: [ntiles][3] {seq, row0, nrows<=16}, rows of one seq
+    const int* tiles;                  // packed prefill: [ntiles][3] {seq, row0, nrows}, rows of one seq (prefill_attn.h)
     int ntiles;
 };
-constexpr int ATTN_TILE_MAXK = 448;   // keys a k_attn_tile block stages in LDS
 void attn_rows(const AttnArgs& a, hipStream_t s);
-// Tiled prefill attention over a.tiles (all rows' keys <= ATTN_TILE_MAXK).
-void attn_rows_tiled(const AttnArgs& a, hipStream_t s);
-// Packed prefill attention over a.tiles on the online-softmax kernel (any key count).
-void attn_rows_flash_tiled(const AttnArgs& a, hipStream_t s);
 // Batched decode attention (one block per head x sequence) whose prologue reduces
 // the split-K QKV slabs of its head: q/k/v = b_in + sum_z slab[z][b][...] (fixed
 // order), appends the new K/V row at position kvlen[b], attends over [0, kvlen[b]].
@@ -181,24 +176,6 @@ struct AttnOutArgs {
     long long* acc_out; long acc_bstride;  // if set: fixed-point adds instead of part
 };
 void attn_outproj(const AttnOutArgs& a, hipStream_t s);
-
-// Fused QKV + attention + out-proj partial, one block per (head, sequence):
-//   x = layer input (LN2 of the previous layer's reduced FFN partials, or h0);
-//   q,k,v of head h from W_in rows; new k,v appended to the cache at kvlen[b];
-//   attention over [0, kvlen] ; part[h][b] = WoT[h-slice]^T o_h.
-struct QkvAttnArgs {
-    int B;
-    const float* src;                              // layer 0: h0 [B][512]
-    const float* part; int n_part; long part_stride; const float* part_bias; const float* part_res;
-    const float* ln_g; const float* ln_b; float* ln_out;   // ln_out: x for the residual
-    const __half* W_in; const float* b_in;
-    float* k; float* v; long seq_stride; int tmax;
-    const int* kvlen; const uint8_t* done;
-    float scale;
-    const __half* WoT;
-    float* attn_part;                              // [16][B][512]
-};
-void qkv_attn_outproj(const QkvAttnArgs& a, hipStream_t s);
 
 // Fused FFN, split-K over the 2048 hidden units (one slice per block):
 //   s1[b] = h[b] + (bo + sum_h attn_part[h][b]);  x = LN1(s1); block 0 writes h1 = x

@@ -293,7 +293,7 @@ __device__ __forceinline__ void gx3_dma(const void* g, void* l) {
 // (W16, kernels.h).  Each product is three MFMAs, a_hi w_hi + a_lo w_hi into acc and
 // a_hi w_lo into accl, and the result is acc + accl 2^-11: a weight keeps ~22 of its
 // 24 significant bits (the reference runs such models with fp32 initializers).
-// WTN > 1 (the large-M form): each wave owns WTN 32 x 32 tiles side by side in N and splits
+// WTN > 1 (no launched form today): each wave owns WTN 32 x 32 tiles side by side in N and splits
 // its A fragment once for all of them, so the split's VALU and the A fragment reads are
 // shared by WTN MFMA pairs; every 32 x 32 tile still runs the one-tile MFMA sequence.
 // XR: blocks that share an A row tile go to one XCD (the guide's bijective remap of the
@@ -447,107 +447,44 @@ __global__ __launch_bounds__(64 * (BM / 32) * (BN / 32 / WTN)) void k_gemm_x3(Ge
     }
 }
 
-// Tile configurations of k_gemm_x3 (GENIE_GEMM_CFG picks one for benchmarks; default: by shape)
-static void launch_x3(const GemmArgs& a, int z, hipStream_t s, int cfg) {
-    auto go = [&](auto kern, int bm, int bn, int threads) {
-        hipLaunchKernelGGL(kern, dim3((a.N + bn - 1) / bn, (a.M + bm - 1) / bm, z), dim3(threads), 0, s, a);
+// The three forms of k_gemm_x3 the engine launches.
+//   SplitW: split fp32 weights (RoBERTa / CN-HuBERT) -- two 32 KB stages with the XCD remap
+//     (64 KB, two blocks per CU); bit-identical to a four-stage form and 0.75x its time on
+//     packed RoBERTa rows (profiles/r04k_gemm_sw.txt).
+//   LargeM: from 1024 blocks of 64 x 64 on (4 per CU) -- two stages with the XCD remap, 48 KB
+//     of LDS, so three blocks (12 waves) share a CU and one block's MFMAs hide another's split
+//     and LDS waits.  On the packed prefill of 64 sentences (22,848 rows) it takes 0.67x
+//     k_gemm_x2's time, bit-identical; one-block-per-CU 128 x 128 forms were slower than
+//     k_gemm_x2 (profiles/r04e_gemm_big.txt).  With a.Ah set, its pre-split-A twin.
+//   SmallM: M <= 512 -- four stages; other tile shapes and ring depths were within 10 %
+//     (profiles/r03f_gemm_sweep.txt).
+enum class X3Form { SplitW, LargeM, SmallM };
+static void launch_x3(const GemmArgs& a, int z, hipStream_t s, X3Form form) {
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((a.N + 63) / 64, (a.M + 63) / 64, z), dim3(256), 0, s, a);
     };
-    if (a.Wl) {   // split weights: 4 x 32 KB stages; cfg 16: 2 stages + XCD remap (64 KB, 2 blocks per CU)
-        if (cfg == 16) go(k_gemm_x3<64, 64, 2, true, 1, true>, 64, 64, 256);
-        else go(k_gemm_x3<64, 64, 4, true>, 64, 64, 256);
-        return;
-    }
-    switch (cfg) {
-        // (r04: the one-block-per-CU 128 x 128 forms, four 32 x 32 tiles per wave, measured
-        // slower than k_gemm_x2 at 22,848 rows and were removed; profiles/r04e_gemm_big.txt)
-        case 13:   // 64 KB: 2 blocks per CU
-            if (a.Ah) go(k_gemm_x3<64, 128, 2, false, 2, true, true>, 64, 128, 256);
-            else go(k_gemm_x3<64, 128, 2, false, 2, true>, 64, 128, 256);
+    switch (form) {
+        case X3Form::SplitW: go(k_gemm_x3<64, 64, 2, true, 1, true>); break;
+        case X3Form::LargeM:
+            if (a.Ah) go(k_gemm_x3<64, 64, 2, false, 1, true, true>);
+            else go(k_gemm_x3<64, 64, 2, false, 1, true>);
             break;
-        case 14:   // 80 KB
-            if (a.Ah) go(k_gemm_x3<128, 64, 2, false, 2, true, true>, 128, 64, 256);
-            else go(k_gemm_x3<128, 64, 2, false, 2, true>, 128, 64, 256);
-            break;
-        case 15:   // 48 KB: 3 per CU
-            if (a.Ah) go(k_gemm_x3<64, 64, 2, false, 1, true, true>, 64, 64, 256);
-            else go(k_gemm_x3<64, 64, 2, false, 1, true>, 64, 64, 256);
-            break;
-        case 1: go(k_gemm_x3<64, 64, 4>, 64, 64, 256); break;
-        case 2: go(k_gemm_x3<32, 64, 4>, 32, 64, 128); break;
-        case 3: go(k_gemm_x3<64, 32, 4>, 64, 32, 128); break;
-        case 4: go(k_gemm_x3<32, 64, 6>, 32, 64, 128); break;
-        case 5: go(k_gemm_x3<64, 64, 6>, 64, 64, 256); break;
-        case 6: go(k_gemm_x3<32, 32, 6>, 32, 32, 64); break;
-        case 7: go(k_gemm_x3<64, 64, 3>, 64, 64, 256); break;
-        case 8: go(k_gemm_x3<32, 64, 3>, 32, 64, 128); break;
-        default: go(k_gemm_x3<64, 64, 4>, 64, 64, 256); break;
+        case X3Form::SmallM: go(k_gemm_x3<64, 64, 4>); break;
     }
 }
-static int gemm_cfg() {
-    static const int c = [] {
-        const char* e = std::getenv("GENIE_GEMM_CFG");
-        return e ? std::atoi(e) : 0;
-    }();
-    return c;
-}
 
-// The large-M configuration (GENIE_GEMM_BIG = its launch_x3 configuration, 0 = k_gemm_x2):
-// k_gemm_x3<64, 64, 2> with the XCD remap -- 48 KB of LDS, so three blocks (12 waves)
-// share a CU and one block's MFMAs hide another's split and LDS waits.  On the packed
-// prefill of 64 sentences (22,848 rows) it takes 0.67x k_gemm_x2's time, bit-identical;
-// the one-block-per-CU 128 x 128 forms were slower than k_gemm_x2 (profiles/r04e_gemm_big.txt).
-// Used from 1024 blocks of 64 x 64 on (4 per CU).
-static int gemm_big_cfg() {
-    static const int c = [] {
-        const char* e = std::getenv("GENIE_GEMM_BIG");
-        return e ? std::atoi(e) : 15;
-    }();
-    return c;
-}
-static bool gemm_big(const GemmArgs& a) {
-    return gemm_big_cfg() != 0 && (long)((a.M + 63) / 64) * ((a.N + 63) / 64) >= 1024;
-}
-
-// Split-weight GEMMs (RoBERTa / CN-HuBERT fp32 weights): the two-stage, two-blocks-per-CU
-// form with the XCD remap (cfg 16, default; bit-identical to the four-stage one, 0.75x its
-// time on packed RoBERTa rows, profiles/r04k_gemm_sw.txt); GENIE_GEMM_SW=0 the four-stage form.
-static int gemm_sw_cfg() {
-    static const int c = [] {
-        const char* e = std::getenv("GENIE_GEMM_SW");
-        return e ? std::atoi(e) : 16;
-    }();
-    return c;
-}
-
-static int gemm_variant() {   // GENIE_GEMM_X3=0: the register-staged k_gemm_x2
-    static const int v = [] {
-        const char* e = std::getenv("GENIE_GEMM_X3");
-        return (e && std::atoi(e) == 0) ? 2 : 3;
-    }();
-    return v;
-}
-
-static bool gemm_x2_enabled() {
-    static const bool on = [] {
-        const char* e = std::getenv("GENIE_GEMM_X2");
-        return !(e && std::atoi(e) == 0);
-    }();
-    return on;
-}
+static bool gemm_big(const GemmArgs& a) { return (long)((a.M + 63) / 64) * ((a.N + 63) / 64) >= 1024; }
 
 bool gemm_w16_supported(int K, long lda, long ldw) { return K % GX_KS == 0 && lda % 4 == 0 && ldw % 8 == 0; }
 
 bool gemm_presplit_path(int M, int N, int K, long lda) {
-    if (K % GX_KS != 0 || lda % 8 != 0 || !gemm_x2_enabled() || gemm_variant() != 3 || gemm_cfg() != 0) return false;
+    if (K % GX_KS != 0 || lda % 8 != 0) return false;
     GemmArgs t{};
     t.M = M; t.N = N;
-    const int c = gemm_big_cfg();
-    return gemm_big(t) && (c == 13 || c == 14 || c == 15);
+    return gemm_big(t);
 }
 
-bool gemm_slabs_supported(int K, long lda, long ldw) {
-    return K % GX_KS == 0 && lda % 4 == 0 && ldw % 8 == 0 && gemm_x2_enabled();
-}
+bool gemm_slabs_supported(int K, long lda, long ldw) { return K % GX_KS == 0 && lda % 4 == 0 && ldw % 8 == 0; }
 
 void gemm_nt(const GemmArgs& a, hipStream_t s) {
     dim3 grid((a.N + 63) / 64, (a.M + 63) / 64);
@@ -558,13 +495,12 @@ void gemm_nt(const GemmArgs& a, hipStream_t s) {
             std::fprintf(stderr, "gemm_nt: split-weight GEMM with unsupported shape K=%d lda=%ld\n", a.K, a.lda);
             std::abort();
         }
-        launch_x3(a, a.mode == EPI_SLAB ? a.ksplit : 1, s, gemm_sw_cfg());
+        launch_x3(a, a.mode == EPI_SLAB ? a.ksplit : 1, s, X3Form::SplitW);
         return;
     }
     // fp16 weights -> split-activation f16 MFMA; the VQ distance GEMM stays on the
     // exact f32 path (its argmin must see the f32 dot products).
-    if (a.w_f16 && a.mode != EPI_VQDIST && a.K % GX_KS == 0 && a.lda % 4 == 0 && a.ldw % 8 == 0 &&
-        gemm_x2_enabled()) {
+    if (a.w_f16 && a.mode != EPI_VQDIST && a.K % GX_KS == 0 && a.lda % 4 == 0 && a.ldw % 8 == 0) {
         if (a.mode == EPI_SLAB) grid.z = a.ksplit;
         // the LDS-DMA pipeline reads A as stored: a slab-summing A prologue stays on k_gemm_x2
         // (M > 512: the register-staged kernel's 128-k steps win once the grid covers the chip)
@@ -572,10 +508,10 @@ void gemm_nt(const GemmArgs& a, hipStream_t s) {
             std::fprintf(stderr, "gemm_nt: pre-split A on a shape without the large-M path (M=%d N=%d)\n", a.M, a.N);
             std::abort();
         }
-        if (a.a_nslab == 0 && a.lda % 4 == 0 && gemm_variant() == 3 && gemm_cfg() == 0 && gemm_big(a))
-            launch_x3(a, grid.z, s, gemm_big_cfg());
-        else if (a.a_nslab == 0 && a.lda % 4 == 0 && gemm_variant() == 3 && (a.M <= 512 || gemm_cfg() != 0))
-            launch_x3(a, grid.z, s, gemm_cfg());
+        if (a.a_nslab == 0 && gemm_big(a))
+            launch_x3(a, grid.z, s, X3Form::LargeM);
+        else if (a.a_nslab == 0 && a.M <= 512)
+            launch_x3(a, grid.z, s, X3Form::SmallM);
         else
             hipLaunchKernelGGL(k_gemm_x2, grid, dim3(256), 0, s, a);
         return;
@@ -928,121 +864,6 @@ void attn_decode_slabs(const AttnDecArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_attn_dec_slabs, dim3(16, a.B), dim3(256), 0, s, a);
 }
 
-// Prefill attention, one sequence: a block = one head x 16 query rows, one row
-// per wave (1024 threads).  The head's keys/values [0, max row_len of the block)
-// are staged in LDS once (36-float rows: conflict-free 16-B reads by 16 lanes);
-// a lane owns keys t = lane + 64 i: scores, softmax numerators and P.V partials
-// stay in registers, and the 32 output dims are reduce-scattered over the wave.
-// Same arithmetic as k_attn_rows ((q s)(k s), exp(x - max), / sum, then P.V);
-// only the summation order differs.  Replaces 16 x N0 blocks that each re-read
-// the head's whole K/V from L2.
-#define AT_ROWS 16
-#define AT_KI 7
-#define AT_MAXK (64 * AT_KI)
-#define AT_KS 36
-__global__ __launch_bounds__(1024) void k_attn_tile(AttnArgs a) {
-    __shared__ __attribute__((aligned(16))) float Ks[AT_MAXK * AT_KS];
-    __shared__ __attribute__((aligned(16))) float Vs[AT_MAXK * AT_KS];
-    __shared__ int rl[AT_ROWS];
-    const int h = blockIdx.x, tid = threadIdx.x;
-    const int lane = tid & 63, w = tid >> 6;
-    // one sequence's rows: a tile of the packed prefill, or rows [16 y, 16 y + 16) of sequence 0
-    int r0, nr;
-    long seq_off = 0;
-    if (a.tiles) {
-        const int* tl = a.tiles + 3 * blockIdx.y;
-        seq_off = (long)tl[0] * a.seq_stride;
-        r0 = tl[1];
-        nr = tl[2];
-    } else {
-        r0 = blockIdx.y * AT_ROWS;
-        nr = min(AT_ROWS, a.rows - r0);
-    }
-    if (tid < AT_ROWS) rl[tid] = tid < nr ? a.row_len[r0 + tid] : 0;
-    __syncthreads();
-    int kmax = 0;
-#pragma unroll
-    for (int i = 0; i < AT_ROWS; ++i) kmax = max(kmax, rl[i]);
-    const float* K = a.k + seq_off + (long)h * a.tmax * 32;
-    const float* V = a.v + seq_off + (long)h * a.tmax * 32;
-    for (int e = tid; e < kmax * 8; e += 1024) {            // 16-B pieces: row e/8, piece e%8
-        const int t = e >> 3, c = e & 7;
-        const float4 kv = *reinterpret_cast<const float4*>(K + (long)t * 32 + 4 * c);
-        const float4 vv = *reinterpret_cast<const float4*>(V + (long)t * 32 + 4 * c);
-        *reinterpret_cast<float4*>(Ks + t * AT_KS + 4 * c) = kv;
-        *reinterpret_cast<float4*>(Vs + t * AT_KS + 4 * c) = vv;
-    }
-    __syncthreads();
-    if (w >= nr) return;
-    const float sc = a.scale;
-    const int r = r0 + w, len = rl[w];
-    float q[32];
-#pragma unroll
-    for (int d = 0; d < 32; d += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(a.q + (long)r * a.ldq + h * 32 + d);
-        q[d] = v.x * sc; q[d + 1] = v.y * sc; q[d + 2] = v.z * sc; q[d + 3] = v.w * sc;
-    }
-    float p[AT_KI];
-    float lmax = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < AT_KI; ++i) {
-        const int t = lane + 64 * i;
-        const float* kr = Ks + min(t, AT_MAXK - 1) * AT_KS;
-        float sacc = 0.f;
-#pragma unroll
-        for (int d = 0; d < 32; d += 4) {
-            const float4 k4 = *reinterpret_cast<const float4*>(kr + d);
-            sacc += q[d] * (k4.x * sc); sacc += q[d + 1] * (k4.y * sc);
-            sacc += q[d + 2] * (k4.z * sc); sacc += q[d + 3] * (k4.w * sc);
-        }
-        p[i] = t < len ? sacc : -INFINITY;
-        lmax = fmaxf(lmax, p[i]);
-    }
-    const float m = wave_max(lmax);
-    float lsum = 0.f;
-#pragma unroll
-    for (int i = 0; i < AT_KI; ++i) {
-        const float e = lane + 64 * i < len ? expf(p[i] - m) : 0.f;
-        p[i] = e;
-        lsum += e;
-    }
-    const float sum = wave_sum(lsum);
-    float o[32];
-#pragma unroll
-    for (int d = 0; d < 32; ++d) o[d] = 0.f;
-#pragma unroll
-    for (int i = 0; i < AT_KI; ++i) {
-        const int t = lane + 64 * i;
-        if (t >= len) continue;                      // rows past len: LDS not staged
-        const float pn = p[i] / sum;                 // normalised numerator
-        const float* vr = Vs + t * AT_KS;
-#pragma unroll
-        for (int d = 0; d < 32; d += 4) {
-            const float4 v4 = *reinterpret_cast<const float4*>(vr + d);
-            o[d] += pn * v4.x; o[d + 1] += pn * v4.y; o[d + 2] += pn * v4.z; o[d + 3] += pn * v4.w;
-        }
-    }
-    // reduce-scatter the 32 dims over the 64 lanes: partner lane ^ (32 >> k) keeps
-    // the half of the dims selected by that lane bit
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const int half = 16 >> k, bit = 32 >> k;
-        const bool up = (lane & bit) != 0;
-#pragma unroll
-        for (int d = 0; d < half; ++d) {
-            const float send = up ? o[d] : o[d + half];
-            const float recv = __shfl_xor(send, bit, 64);
-            o[d] = (up ? o[d + half] : o[d]) + recv;
-        }
-    }
-    // lane now holds dim (bits 5..1 of lane, MSB first) summed over lanes with the
-    // same bit 0; the pair lane ^ 1 completes the sum
-    const float tot = o[0] + __shfl_xor(o[0], 1, 64);
-    const int d = ((lane >> 5) & 1) * 16 + ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 +
-                  ((lane >> 1) & 1);
-    if ((lane & 1) == 0) a.out[(long)r * a.ldo + h * 32 + d] = tot;
-}
-
 // Prefill attention of one sequence, online softmax over 64-key chunks: a block
 // = one head x 16 query rows (4 waves x 4 rows).  The head's K/V chunk is staged
 // once per block in LDS (rows padded to 36 floats: conflict-free 16-B reads by
@@ -1171,239 +992,6 @@ __global__ __launch_bounds__(256) void k_attn_flash(AttnArgs a) {
         float* dst = a.out + (long)(r0 + row) * a.ldo + h * 32 + pd;
         dst[0] = o.x / lr;
         dst[1] = o.y / lr;
-    }
-}
-
-// Prefill attention on the f16 MFMA (stage#91-96 per head): a block = one head x
-// 32 NW query rows of one sequence, wave w owns rows 32 w .. 32 w + 31.  Operands are
-// split hi + lo into fp16 (three MFMAs per product, f32 accumulation: the dropped term
-// is ~2^-22 of each product, as in the split-activation GEMMs).  Per 64-key chunk:
-//   S^T = K Q^T  (A = the chunk's K rows, B = the wave's q rows): lane l holds the
-//                scores of query row l % 32 for 32 of the 64 keys, the lane l ^ 32 the
-//                other 32, so the online softmax (stage#95) needs one cross-lane step;
-//   O^T += V^T P^T  (B = the P values straight from the S^T accumulator registers, the
-//                16 keys of a k-step taken in the accumulator's key order and V^T read
-//                in that same order), so O^T's lane keeps its own query row and the
-//                running rescale stays in-lane.
-// K and V chunks arrive raw (f32) by LDS-DMA in a ring of AM_RING chunks, issued
-// AM_RING - 1 chunks ahead of use; each is then split into the fp16 hi / lo planes of K
-// (scaled by s, as q) and V^T that the MFMA fragments read.
-// A block reads its head's K/V once per 32 NW rows (k_attn_flash: once per 16).  Used by
-// the packed (batched) prefill: 128-row tiles of one sequence.
-#define AM_KC 64
-#define AM_KR 40   // K plane row stride (halfs): 32 dims + pad
-#define AM_VR 72   // V^T plane row stride (halfs): 64 keys + pad
-#define AM_RING 3
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void k_attn_mfma(AttnArgs a) {
-    constexpr int NT = 64 * NW, ROWS = 32 * NW, NI = AM_KC * 8 / NT;   // float4 items per thread (K and V each)
-    constexpr int DPW = 16 / NW;                                       // DMA instructions per wave per chunk
-    __shared__ __attribute__((aligned(16))) float Kr[AM_RING][AM_KC * 32];   // raw chunks (LDS-DMA ring)
-    __shared__ __attribute__((aligned(16))) float Vr[AM_RING][AM_KC * 32];
-    __shared__ __attribute__((aligned(16))) _Float16 Kh[AM_KC * AM_KR];
-    __shared__ __attribute__((aligned(16))) _Float16 Kl[AM_KC * AM_KR];
-    __shared__ __attribute__((aligned(16))) _Float16 Vh[32 * AM_VR];
-    __shared__ __attribute__((aligned(16))) _Float16 Vl[32 * AM_VR];
-    __shared__ int rl[ROWS];
-    __shared__ int kmax_s;
-    const int h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int r32 = lane & 31, hs = lane >> 5;
-    int r0 = blockIdx.y * ROWS, nr = min(ROWS, a.rows - r0);
-    long kvbase = (long)h * a.tmax * 32;
-    if (a.tiles) {   // packed prefill: tile {sequence, first row, rows <= ROWS}
-        const int* tl = a.tiles + 3 * blockIdx.y;
-        kvbase += (long)tl[0] * a.seq_stride;
-        r0 = tl[1];
-        nr = tl[2];
-    }
-    const float sc = a.scale;
-    if (tid == 0) kmax_s = 0;
-    __syncthreads();
-    if (tid < ROWS) {
-        rl[tid] = tid < nr ? a.row_len[r0 + tid] : 0;
-        atomicMax(&kmax_s, rl[tid]);
-    }
-    __syncthreads();
-    const int kmax = kmax_s;
-    const int row = 32 * w + r32;                  // this lane's query row (of the block)
-    const int len = rl[row];
-    const bool wave_rows = 32 * w < nr;            // a wave past the tile's rows only stages
-    // q fragments (B of S^T): row `row`, dims 16 ks + 8 hs .. + 7, scaled by s
-    h16x8 qh[2], ql[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        float4 x0 = make_float4(0.f, 0.f, 0.f, 0.f), x1 = x0;
-        if (row < nr) {
-            const float* qp = a.q + (long)(r0 + row) * a.ldq + h * 32 + 16 * ks + 8 * hs;
-            x0 = *reinterpret_cast<const float4*>(qp);
-            x1 = *reinterpret_cast<const float4*>(qp + 4);
-        }
-        x0 = make_float4(x0.x * sc, x0.y * sc, x0.z * sc, x0.w * sc);
-        x1 = make_float4(x1.x * sc, x1.y * sc, x1.z * sc, x1.w * sc);
-        split8(x0, x1, qh[ks], ql[ks]);
-    }
-    const float* K = a.k + kvbase;
-    const float* V = a.v + kvbase;
-    // chunk c -> ring slot c % AM_RING: DMA instruction j (8 keys x 32 dims, 1 KB) of K and of
-    // V by wave j % NW; keys past kmax read row 0 (in bounds; zeroed by the split)
-    auto dma = [&](int c) {
-        const int slot = c % AM_RING;
-#pragma unroll
-        for (int i = 0; i < 8 / NW; ++i) {
-            const int j = w + NW * i, key = AM_KC * c + 8 * j + (lane >> 3);
-            const long src = (long)(key < kmax ? key : 0) * 32 + 4 * (lane & 7);
-            gx3_dma(K + src, &Kr[slot][j * 256]);
-            gx3_dma(V + src, &Vr[slot][j * 256]);
-        }
-    };
-    // ring slot of chunk c -> the split planes (keys past kmax: 0)
-    auto split_chunk = [&](int c) {
-        const int slot = c % AM_RING, k0 = AM_KC * c;
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int e = tid + NT * i, t = e >> 3, cc = e & 7;
-            const bool ok = k0 + t < kmax;
-            const float4 kv4 = *reinterpret_cast<const float4*>(&Kr[slot][t * 32 + 4 * cc]);
-            const float4 vv4 = *reinterpret_cast<const float4*>(&Vr[slot][t * 32 + 4 * cc]);
-            const float kx[4] = {ok ? kv4.x * sc : 0.f, ok ? kv4.y * sc : 0.f, ok ? kv4.z * sc : 0.f,
-                                 ok ? kv4.w * sc : 0.f};
-            const float vx[4] = {ok ? vv4.x : 0.f, ok ? vv4.y : 0.f, ok ? vv4.z : 0.f, ok ? vv4.w : 0.f};
-            _Float16 khi[4], klo[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                khi[j] = (_Float16)kx[j];
-                klo[j] = (_Float16)(kx[j] - (float)khi[j]);
-                const _Float16 vh = (_Float16)vx[j];
-                Vh[(4 * cc + j) * AM_VR + t] = vh;
-                Vl[(4 * cc + j) * AM_VR + t] = (_Float16)(vx[j] - (float)vh);
-            }
-            *reinterpret_cast<uint2*>(&Kh[t * AM_KR + 4 * cc]) = *reinterpret_cast<const uint2*>(khi);
-            *reinterpret_cast<uint2*>(&Kl[t * AM_KR + 4 * cc]) = *reinterpret_cast<const uint2*>(klo);
-        }
-    };
-    float m = -INFINITY, l = 0.f;
-    f32x16 o;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) o[i] = 0.f;
-    const int nch = (kmax + AM_KC - 1) / AM_KC;
-    if (nch > 0) {
-        for (int c = 0; c < AM_RING && c < nch; ++c) dma(c);
-        gx3_wait<DPW>(min(AM_RING, nch) - 1);      // chunk 0 (this wave's part) landed
-        __syncthreads();
-        split_chunk(0);
-    }
-    __syncthreads();
-    for (int c = 0; c < nch; ++c) {
-        const int k0 = c * AM_KC;
-        if (wave_rows) {
-            // ---- S^T: keys 32 T + {8 (i / 4) + 4 hs + i % 4} of row `row` in s[T][i]
-            f32x16 s[2];
-#pragma unroll
-            for (int T = 0; T < 2; ++T) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) s[T][i] = 0.f;
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const int off = (32 * T + r32) * AM_KR + 16 * ks + 8 * hs;
-                    const h16x8 ah = *reinterpret_cast<const h16x8*>(&Kh[off]);
-                    const h16x8 al = *reinterpret_cast<const h16x8*>(&Kl[off]);
-                    s[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, qh[ks], s[T], 0, 0, 0);
-                    s[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, ql[ks], s[T], 0, 0, 0);
-                    s[T] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, qh[ks], s[T], 0, 0, 0);
-                }
-            }
-            // ---- online softmax of the row over the chunk (keys >= len: -inf)
-            float mc = -INFINITY;
-#pragma unroll
-            for (int T = 0; T < 2; ++T)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int key = k0 + 32 * T + 8 * (i >> 2) + 4 * hs + (i & 3);
-                    if (key >= len) s[T][i] = -INFINITY;
-                    mc = fmaxf(mc, s[T][i]);
-                }
-            mc = fmaxf(mc, __shfl_xor(mc, 32, 64));
-            const float mn = fmaxf(m, mc);
-            const float corr = mn == -INFINITY ? 1.f : __expf(m - mn);
-            float ps = 0.f;
-#pragma unroll
-            for (int T = 0; T < 2; ++T)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float p = s[T][i] == -INFINITY ? 0.f : __expf(s[T][i] - mn);
-                    s[T][i] = p;
-                    ps += p;
-                }
-            ps += __shfl_xor(ps, 32, 64);
-            l = l * corr + ps;
-            m = mn;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) o[i] *= corr;
-            // ---- O^T += V^T P^T, k-step (T, g): keys 32 T + 16 g + {0..3, 8..11} (+4 for hs = 1)
-#pragma unroll
-            for (int T = 0; T < 2; ++T)
-#pragma unroll
-                for (int g = 0; g < 2; ++g) {
-                    h16x8 ph, pl;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float p = s[T][8 * g + j];
-                        ph[j] = (_Float16)p;
-                        pl[j] = (_Float16)(p - (float)ph[j]);
-                    }
-                    const int kb = 32 * T + 16 * g + 4 * hs;
-                    const _Float16* vh = &Vh[r32 * AM_VR + kb];
-                    const _Float16* vl = &Vl[r32 * AM_VR + kb];
-                    h16x8 ah, al;
-                    const uint2 h0 = *reinterpret_cast<const uint2*>(vh), h1 = *reinterpret_cast<const uint2*>(vh + 8);
-                    const uint2 l0 = *reinterpret_cast<const uint2*>(vl), l1 = *reinterpret_cast<const uint2*>(vl + 8);
-                    ah = __builtin_bit_cast(h16x8, make_uint4(h0.x, h0.y, h1.x, h1.y));
-                    al = __builtin_bit_cast(h16x8, make_uint4(l0.x, l0.y, l1.x, l1.y));
-                    o = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, ph, o, 0, 0, 0);
-                    o = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, pl, o, 0, 0, 0);
-                    o = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, ph, o, 0, 0, 0);
-                }
-        }
-        if (c + 1 < nch) {
-            // chunk c + 1 landed (this wave's part; chunk c + 2 may stay in flight), then every
-            // wave's part and every wave done with the split planes of chunk c
-            gx3_wait<DPW>(min(c + AM_RING - 1, nch - 1) - (c + 1));
-            __syncthreads();
-            if (c + AM_RING < nch) dma(c + AM_RING);   // into chunk c's slot (split last round)
-            split_chunk(c + 1);
-            __syncthreads();
-        }
-    }
-    // ---- O^T lane: row `row`, dims 8 (i / 4) + 4 hs + i % 4
-    if (row < nr) {
-        float* dst = a.out + (long)(r0 + row) * a.ldo + h * 32 + 4 * hs;
-        const float rl_ = 1.f / l;
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<float4*>(dst + 8 * g) =
-                make_float4(o[4 * g] * rl_, o[4 * g + 1] * rl_, o[4 * g + 2] * rl_, o[4 * g + 3] * rl_);
-    }
-}
-
-// GENIE_ATTN_MFMA=1: the packed prefill's attention on the split-fp16 MFMA kernel.  Off by
-// default since r05: its rounding differs from the f32 online-softmax kernels a sentence's
-// own prefill runs, so a batched generate could pick a different token than the same
-// sentence alone (and than the oracle) at a near-tie -- found on one input of the B = 64
-// test set (profiles/r05x_batched_near_tie.txt).  With the f32 kernels a batch's tokens
-// are each sentence's own.
-bool attn_mfma_on() {
-    static const bool on = [] { const char* e = std::getenv("GENIE_ATTN_MFMA"); return e && std::atoi(e) != 0; }();
-    return on;
-}
-
-void attn_rows_mfma(const AttnArgs& a, int rows_per_block, hipStream_t s) {
-    if (a.tiles ? a.ntiles <= 0 : a.rows <= 0) return;
-    if (rows_per_block == 128) {
-        const dim3 grid(16, a.tiles ? a.ntiles : (a.rows + 127) / 128);
-        hipLaunchKernelGGL(k_attn_mfma<4>, grid, dim3(256), 0, s, a);
-    } else {
-        const dim3 grid(16, a.tiles ? a.ntiles : (a.rows + 63) / 64);
-        hipLaunchKernelGGL(k_attn_mfma<2>, grid, dim3(128), 0, s, a);
     }
 }
 
@@ -1729,24 +1317,12 @@ void attn_rows_mf32(const AttnArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_attn_mf32<MF32_NW>, dim3(16, a.ntiles), dim3(64 * MF32_NW), 0, s, a);
 }
 
-// One sequence's prefill (rows = its N0 positions) on k_attn_mf32, one wave per 32 rows.
-// Opt-in (GENIE_PREFILL_MF32=1): bit-identical to k_attn_flash, but no faster at ~300 rows
-// in the single-sentence stream (15.28 vs 15.32 ms per utterance, profiles/r05m_prefill_mf32_ab.txt)
-bool prefill_mf32_on() {
-    static const bool on = [] { const char* e = std::getenv("GENIE_PREFILL_MF32"); return e && std::atoi(e) != 0; }();
-    return on;
-}
-void attn_rows_mf32_seq(const AttnArgs& a, hipStream_t s) {
-    if (a.rows <= 0) return;
-    hipLaunchKernelGGL(k_attn_mf32<1>, dim3(16, (a.rows + 31) / 32), dim3(64), 0, s, a);
-}
-
 void attn_rows_rowlane(const AttnArgs& a, hipStream_t s) {
     if (a.ntiles <= 0) return;
     hipLaunchKernelGGL(k_attn_rowlane<ROWLANE_NW>, dim3(16, a.ntiles), dim3(64 * ROWLANE_NW), 0, s, a);
 }
 
-// (One sequence's prefill stays on k_attn_flash: at ~300 rows the MFMA kernel's 80
+// (One sequence's prefill stays on k_attn_flash: at ~300 rows a split-fp16 MFMA kernel's 80
 // blocks of 64 rows were no faster -- prefill 2.00 vs 1.91 ms, profiles/r04q_prefill_attn.txt.)
 void attn_rows(const AttnArgs& a, hipStream_t s) {
     if (a.rows <= 0) return;
@@ -1758,28 +1334,7 @@ void attn_rows(const AttnArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(k_attn_flash, dim3(16, (a.rows + AF_ROWS - 1) / AF_ROWS), dim3(256), 0, s, a);
         return;
     }
-    // prefill of one sequence (row r sees keys [0, row_len[r]) <= rows).  Off by
-    // default: measured slower than k_attn_rows at N0 = 225 (prefill 2.14 vs 1.83 ms)
-    static const bool tile = [] {
-        const char* e = std::getenv("GENIE_ATTN_TILE");
-        return e && std::atoi(e) != 0;
-    }();
-    if (tile && !a.row_seq && !a.row_skip && a.rows <= AT_MAXK) {
-        hipLaunchKernelGGL(k_attn_tile, dim3(16, (a.rows + AT_ROWS - 1) / AT_ROWS), dim3(1024), 0, s, a);
-        return;
-    }
     hipLaunchKernelGGL(k_attn_rows, dim3(16, a.rows), dim3(256), 0, s, a, 0);
-}
-
-void attn_rows_tiled(const AttnArgs& a, hipStream_t s) {
-    if (a.ntiles <= 0) return;
-    static_assert(AT_MAXK == ATTN_TILE_MAXK, "tile key capacity");
-    hipLaunchKernelGGL(k_attn_tile, dim3(16, a.ntiles), dim3(1024), 0, s, a);
-}
-
-void attn_rows_flash_tiled(const AttnArgs& a, hipStream_t s) {
-    if (a.ntiles <= 0) return;
-    hipLaunchKernelGGL(k_attn_flash, dim3(16, a.ntiles), dim3(256), 0, s, a);
 }
 
 void attn_rows_plus(const AttnArgs& a, int len_add, hipStream_t s) {

@@ -334,179 +334,4 @@ void ffn_fused(const FfnArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t sto
     else launch_ffn<64>(a, s, start, stop);   // nslices == 32
 }
 
-// ---------------------------------------------------------------------------
-// QKV (head slice) + attention + out-proj partial in one launch.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_qkv_attn(QkvAttnArgs a) {
-    __shared__ float xs[512];
-    __shared__ float qkv[3][32];
-    __shared__ float os[32];
-    __shared__ float red[16];
-    __shared__ float redm[4];
-    __shared__ float redl[4][8];
-    __shared__ float reda[4][32];
-    __shared__ float ored[4][512];
-    const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    if (a.done && a.done[b]) return;
-    // 1. weight prefetch: W_in rows {q,k,v} x (h*32 + w*8 + r), 16 B per lane; WoT slice
-    uint4 wq[3][8];
-#pragma unroll
-    for (int m = 0; m < 3; ++m)
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-            wq[m][r] = *reinterpret_cast<const uint4*>(a.W_in + (long)(m * 512 + h * 32 + w * 8 + r) * 512 + lane * 8);
-    uint4 wo[8];
-    {
-        const __half* base = a.WoT + (long)(h * 32) * 512 + 8 * lane;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) wo[i] = *reinterpret_cast<const uint4*>(base + (long)(w + 4 * i) * 512);
-    }
-    // 2. layer input
-    if (a.part) {
-        float p0 = a.part_bias[tid], p1 = a.part_bias[tid + 256];
-        for (int j0 = 0; j0 < a.n_part; j0 += 16) {
-            float q0[16], q1[16];
-#pragma unroll
-            for (int jj = 0; jj < 16; ++jj) {
-                const float* pp = a.part + (long)(j0 + jj) * a.part_stride + (long)b * 512;
-                q0[jj] = pp[tid];
-                q1[jj] = pp[tid + 256];
-            }
-#pragma unroll
-            for (int jj = 0; jj < 16; ++jj) { p0 += q0[jj]; p1 += q1[jj]; }
-        }
-        float v0[1] = {a.part_res[(long)b * 512 + tid] + p0};
-        float v1[1] = {a.part_res[(long)b * 512 + tid + 256] + p1};
-        float mean[1], den[1];
-        block_meanvar512<1>(v0, v1, 1, mean, den, red);
-        const float o0 = (v0[0] - mean[0]) / den[0] * a.ln_g[tid] + a.ln_b[tid];
-        const float o1 = (v1[0] - mean[0]) / den[0] * a.ln_g[tid + 256] + a.ln_b[tid + 256];
-        xs[tid] = o0;
-        xs[tid + 256] = o1;
-        if (h == 0) {
-            a.ln_out[(long)b * 512 + tid] = o0;
-            a.ln_out[(long)b * 512 + tid + 256] = o1;
-        }
-    } else {
-        xs[tid] = a.src[(long)b * 512 + tid];
-        xs[tid + 256] = a.src[(long)b * 512 + tid + 256];
-    }
-    __syncthreads();
-    // 3. q, k, v of this head (24 rows per wave)
-    {
-        const float4 x0 = *reinterpret_cast<const float4*>(&xs[lane * 8]);
-        const float4 x1 = *reinterpret_cast<const float4*>(&xs[lane * 8 + 4]);
-#pragma unroll
-        for (int m = 0; m < 3; ++m)
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                float wf[8];
-                h8_to_f8(wq[m][r], wf);
-                float sacc = 0.f;
-                sacc += wf[0] * x0.x; sacc += wf[1] * x0.y; sacc += wf[2] * x0.z; sacc += wf[3] * x0.w;
-                sacc += wf[4] * x1.x; sacc += wf[5] * x1.y; sacc += wf[6] * x1.z; sacc += wf[7] * x1.w;
-                sacc = wave_sum_dpp(sacc);
-                if (lane == 0) {
-                    const int row = m * 512 + h * 32 + w * 8 + r;
-                    qkv[m][w * 8 + r] = a.b_in[row] + sacc;
-                }
-            }
-    }
-    __syncthreads();
-    const int kvl = a.kvlen[b];
-    float* Kc = a.k + (long)b * a.seq_stride + (long)h * a.tmax * 32;
-    float* Vc = a.v + (long)b * a.seq_stride + (long)h * a.tmax * 32;
-    if (tid < 32) Kc[(long)kvl * 32 + tid] = qkv[1][tid];
-    else if (tid < 64) Vc[(long)kvl * 32 + tid - 32] = qkv[2][tid - 32];
-    // 4. attention over [0, kvl] (key kvl taken from LDS)
-    const float sc = a.scale;
-    const int c = lane & 7, g = (w << 3) | (lane >> 3);
-    const float q0 = qkv[0][4 * c] * sc, q1 = qkv[0][4 * c + 1] * sc;
-    const float q2 = qkv[0][4 * c + 2] * sc, q3 = qkv[0][4 * c + 3] * sc;
-    const float4 knew = make_float4(qkv[1][4 * c], qkv[1][4 * c + 1], qkv[1][4 * c + 2], qkv[1][4 * c + 3]);
-    const float4 vnew = make_float4(qkv[2][4 * c], qkv[2][4 * c + 1], qkv[2][4 * c + 2], qkv[2][4 * c + 3]);
-    const int len = kvl + 1;
-    float mt = -INFINITY, l = 0.f, o0 = 0.f, o1 = 0.f, o2 = 0.f, o3 = 0.f;
-    constexpr int U = 4;
-    for (int base = 0; base < len; base += 32 * U) {
-        float4 kk[U], vv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int t = min(base + u * 32 + g, kvl - 1);
-            kk[u] = *reinterpret_cast<const float4*>(Kc + (long)t * 32 + 4 * c);
-            vv[u] = *reinterpret_cast<const float4*>(Vc + (long)t * 32 + 4 * c);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int t = base + u * 32 + g;
-            if (t == kvl) { kk[u] = knew; vv[u] = vnew; }
-            float sv = q0 * (kk[u].x * sc);
-            sv += q1 * (kk[u].y * sc);
-            sv += q2 * (kk[u].z * sc);
-            sv += q3 * (kk[u].w * sc);
-            sv += __shfl_xor(sv, 1, 64);
-            sv += __shfl_xor(sv, 2, 64);
-            sv += __shfl_xor(sv, 4, 64);
-            if (t < len) {
-                const float mn = fmaxf(mt, sv);
-                const float f = expf(mt - mn);
-                const float p = expf(sv - mn);
-                l = l * f + p;
-                o0 = o0 * f + p * vv[u].x;
-                o1 = o1 * f + p * vv[u].y;
-                o2 = o2 * f + p * vv[u].z;
-                o3 = o3 * f + p * vv[u].w;
-                mt = mn;
-            }
-        }
-    }
-    const float bm = wave_max(mt);
-    if (lane == 0) redm[w] = bm;
-    __syncthreads();
-    const float m = fmaxf(fmaxf(redm[0], redm[1]), fmaxf(redm[2], redm[3]));
-    const float fsc = mt == -INFINITY ? 0.f : expf(mt - m);
-    l *= fsc; o0 *= fsc; o1 *= fsc; o2 *= fsc; o3 *= fsc;
-#pragma unroll
-    for (int x = 8; x < 64; x <<= 1) {
-        l += __shfl_xor(l, x, 64);
-        o0 += __shfl_xor(o0, x, 64);
-        o1 += __shfl_xor(o1, x, 64);
-        o2 += __shfl_xor(o2, x, 64);
-        o3 += __shfl_xor(o3, x, 64);
-    }
-    if (lane < 8) {
-        reda[w][4 * lane] = o0; reda[w][4 * lane + 1] = o1;
-        reda[w][4 * lane + 2] = o2; reda[w][4 * lane + 3] = o3;
-        redl[w][lane] = l;
-    }
-    __syncthreads();
-    if (tid < 32) {
-        const float L = (redl[0][0] + redl[1][0]) + (redl[2][0] + redl[3][0]);
-        os[tid] = ((reda[0][tid] + reda[1][tid]) + (reda[2][tid] + reda[3][tid])) / L;
-    }
-    __syncthreads();
-    // 5. out-proj partial
-    float r8[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) r8[k] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        float wf[8];
-        h8_to_f8(wo[i], wf);
-        const float ov = os[w + 4 * i];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) r8[k] += wf[k] * ov;
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) ored[w][8 * lane + k] = r8[k];
-    __syncthreads();
-    float* dst = a.attn_part + ((long)h * a.B + b) * 512;
-    dst[tid] = (ored[0][tid] + ored[1][tid]) + (ored[2][tid] + ored[3][tid]);
-    dst[tid + 256] = (ored[0][tid + 256] + ored[1][tid + 256]) + (ored[2][tid + 256] + ored[3][tid + 256]);
-}
-
-void qkv_attn_outproj(const QkvAttnArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_qkv_attn, dim3(16, a.B), dim3(256), 0, s, a);
-}
-
 }  // namespace gsv

@@ -33,9 +33,6 @@
 namespace gsv {
 namespace {
 
-#ifndef PERSISTM_LATE_W
-#define PERSISTM_LATE_W 0
-#endif
 constexpr int MG = 4;           // sequences per group
 constexpr int NSG_MAX = 16;     // groups (x 16 workgroups: the whole chip)
 constexpr int GWM = 16;         // workgroups per group
@@ -698,10 +695,7 @@ __device__ void run_group(const PersistArgs& a, const WsSeq& base, SharedM& sh, 
 #pragma unroll
                 for (int t = 0; t < 4; ++t) wo[t] = ldg16(P.w_out + (long)(64 * w + 16 * t + n16) * 512 + r * 32 + k8, 0);
             };
-            // PERSISTM_LATE_W (A/B build, tools/r06g_late_w.hip): the layer's weight loads after
-            // its gathers, so no gather polls behind ~128 KB of weight loads in its own wave's queue
-            constexpr bool late_w = PERSISTM_LATE_W != 0;
-            if constexpr (!late_w) load_wq();
+            load_wq();
             if (l == 0) {   // x_0 = E_audio[tok] + alpha pe[n]
                 bool ok = true;
                 const int nl = __builtin_popcount(live);
@@ -725,7 +719,6 @@ __device__ void run_group(const PersistArgs& a, const WsSeq& base, SharedM& sh, 
                               Q.b2, Q.n2w))
                     return;
             }
-            if constexpr (late_w) load_wq();
             PMSTAMP(l == 12, 1);
             {
                 float mean[MG], rden[MG];
@@ -907,11 +900,10 @@ __device__ void run_group(const PersistArgs& a, const WsSeq& base, SharedM& sh, 
                 ffB = ldg(a.fold, (long)l * FOLD_LAYER + 3072 + r * 128 + w * 16 + m16);
                 ffC = ldg(a.fold, (long)l * FOLD_LAYER + 5120 + r * 128 + w * 16 + m16);
             };
-            if constexpr (!late_w) load_w1();
+            load_w1();
             if (!gather_m(a, base, sh, live, tag, [&](int i) { return base.seq(g + i * nsg).PA(s, l, 0); }, P.b_out,
                           P.n1w, s == 1 && l == 0 && g == 0 && r == 0))
                 return;
-            if constexpr (late_w) load_w1();
             PMSTAMP(l == 12, 5);
             {
                 const int tid2 = opaque_tid(), lane2 = tid2 & 63;

@@ -67,9 +67,6 @@ struct ConvArgs {
     // f16-split path: 0 = the cost model's tile; 1..4 = tile candidate 0..3 of launch_h (option
     // "convh_tile", tests)
     int tile_force;
-    // f16-split path: > 0 = the CUs of the stream; large grids then run the persistent tile
-    // loop (two blocks per CU) instead of one block per tile (option "convh_persist")
-    int persist;
     // f16-split path: > 0 = the CUs of the stream; the wide MRF convs (Cin 64 / 128) then run
     // the weight-stationary persistent form, k_conv_ws (option "convh_ws")
     int ws;

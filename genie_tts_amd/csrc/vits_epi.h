@@ -164,12 +164,9 @@ __device__ __forceinline__ void conv_epilogue16_(const ConvArgs& a, int cobase, 
     }
 }
 
-// The lean form for the persistent conv (vits_convh.hip, PERS), whose epilogue sits inside
-// its tile loop: modes STORE, RESID, ACC_FIRST / ADD / MEAN only (the MRF convs and the
-// ConvTranspose), the same arithmetic order as conv_epilogue16_.
-__device__ __forceinline__ bool conv_epilogue_lean_mode(int mode) {
-    return mode == CV_STORE || mode == CV_RESID || mode == CV_ACC_FIRST || mode == CV_ACC_ADD || mode == CV_ACC_MEAN;
-}
+// The lean form for the weight-stationary conv (k_conv_ws, vits_convh.hip), whose epilogue sits
+// inside its tile loop: modes STORE, RESID, ACC_FIRST / ADD / MEAN only (the MRF convs), the
+// same arithmetic order as conv_epilogue16_.
 __device__ __forceinline__ void conv_epilogue16_lean(const ConvArgs& a, int cobase, int t, int ph,
                                                      const float (&val)[16]) {
     const int tp = t * a.o_tstride + a.o_toff + ph;

@@ -377,14 +377,13 @@ int gsv_request_stop(gsv_engine* eng, int32_t on);
  * stream runs the front's text branch beside its SSL branch and a generator stage's three resblocks
  * on three streams; 0: in order on one stream; bit-identical),
  * "pf_delay" (0: a B = 1 decode workgroup waits N x s_sleep(32)
- * between its publish and its next-layer refill), A/B options measured and left off:
- * "convh_persist" (the large split-fp16 convs as a persistent tile loop, bit-identical),
+ * between its publish and its next-layer refill),
  * "convh_ws" (the 7- / 11-tap MRF convs with 64 / 128 input channels weight-stationary, k_conv_ws:
- * 0 off, 1 in every batched generator pass, 2 -- the default -- only in a synchronous
- * gsv_vits_decode_batch, whose vocoder has the GPU to itself;
- * bit-identical),
- * "vocoder_first" (a batched decode waits for the running vocoder batch), "lanes_all_cus"
- * (under vocoder_cus, the batch lanes on every CU), "knob0".."knob3" (decode tuning variants),
+ * 2 -- the default -- in a synchronous gsv_vits_decode_batch, whose vocoder has the GPU to
+ * itself; 1 in every batched generator pass; 0 off; bit-identical),
+ * A/B options measured and left off: "vocoder_first" (a batched decode waits for the running
+ * vocoder batch), "lanes_all_cus" (under vocoder_cus, the batch lanes on every CU),
+ * "knob0".."knob3" (decode tuning variants),
  * test hooks ("persist_spin_ticks", "persist1_f16_limit", "sv_f16_limit", "convh_tile":
  * 1..4 forces that k_conv_h tile candidate, 0 the cost model).  "ptrace": 1 allocates per-workgroup phase stamps of the persistent
  * launch (step 8, layer 12), read back with gsv_debug_ptrace ([256 workgroups][16

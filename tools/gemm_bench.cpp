@@ -1,8 +1,7 @@
 // Time the engine's fp16-weight GEMM (gsv::gemm_nt) on the shapes the engine runs:
 // T2S prefill (N0 = 225 rows), batched decode (B = 64), RoBERTa (40 tokens), CN-HuBERT
 // (300 frames), the packed prefill of 64 sentences (22848 rows).  Prints per-shape microseconds (hipEvents over 200 launches), the max
-// error against a double-precision host GEMM on sampled entries, and a bit hash of C
-// (identical hashes under GENIE_GEMM_X3=0 / 1 = bit-identical kernels).
+// error against a double-precision host GEMM on sampled entries, and a bit hash of C.
 // Build: hipcc -O3 --offload-arch=gfx950 tools/gemm_bench.cpp -Igenie_tts_amd/csrc
 //        -Lgenie_tts_amd/_lib -lgenie_engine -Wl,-rpath,$PWD/genie_tts_amd/_lib -o tools/gemm_bench
 #include <hip/hip_runtime.h>
