@@ -128,7 +128,10 @@ gsv_engine::~gsv_engine() {
     drop_sides();
     if (own_stream && stream) hipStreamDestroy(stream);
     if (vstream) hipStreamDestroy(vstream);
-    for (hipEvent_t e : {vev_in, vev_done, pf_in, pf_done, pf_copied, pf_fork, pf_ev[0], pf_ev[1], pf_ev[2]})
+    if (lane1.st) hipStreamDestroy(lane1.st);
+    if (lane1.ring) hipFree(lane1.ring);
+    if (lane1.err) hipFree(lane1.err);
+    for (hipEvent_t e : {vev_in, vev_done, pf_in, pf_done, pf_copied, pf_fork, pf_ev[0], pf_ev[1], pf_ev[2], ws_free})
         if (e) hipEventDestroy(e);
     if (done_host) hipHostFree(done_host);
     for (auto& e : kev) if (e) hipEventDestroy(e);
@@ -184,7 +187,7 @@ gsv_engine::~gsv_engine() {
 
 hipError_t gsv_engine::sync_own_streams() {
     hipError_t r = hipSuccess;
-    for (hipStream_t s : {stream, vstream})
+    for (hipStream_t s : {stream, lane1.st, vstream})
         if (s && r == hipSuccess) r = hipStreamSynchronize(s);
     {
         std::lock_guard<std::mutex> lk(side_mu);
@@ -1125,7 +1128,19 @@ int gsv_engine::decode_persistent(int B, const gsv_sampler* sp, hipStream_t st) 
 // on the vocoder CUs right after the kernel.  one: the single-sequence kernel
 // (t2s_persist1.hip) instead of the general one.
 int gsv_engine::persist_enqueue(int B, const gsv_sampler* sp, hipStream_t st, int* perr_dst,
-                                hipEvent_t k0, hipEvent_t k1, char* res_dst, int res_b) {
+                                hipEvent_t k0, hipEvent_t k1, char* res_dst, int res_b, int lane) {
+    // lane 1 (a started single-utterance generate beside the one on the engine stream): its own
+    // ring, epoch, error word and slot; the kernel sees "sequence 0" at the slot's addresses
+    if (lane != 0 && (B != 1 || st != lane1.st || max_batch <= LaneBook::slot_of(lane)))
+        return set_error(GSV_E_STATE, "decode lane 1 runs single-utterance launches on its own stream");
+    void*& pws = lane ? lane1.ring : this->pws;
+    size_t& pws_bytes = lane ? lane1.ring_bytes : this->pws_bytes;
+    int lane1_layout = -1;
+    int& pws_batch = lane ? lane1_layout : this->pws_batch;
+    unsigned& pepoch = lane ? lane1.epoch : this->pepoch;
+    int*& perr = lane ? lane1.err : this->perr;
+    const int slot = LaneBook::slot_of(lane);
+    const long slot_kv = (long)slot * 16 * tmax * 32;
     // One launch runs every loop step (t2s_persist1.hip).  Hand-offs are tagged
     // granules in a ring; the launch epoch in the tag makes the ring reusable
     // without zeroing (re-zeroed when the epoch wraps or the layout changes).
@@ -1160,20 +1175,21 @@ int gsv_engine::persist_enqueue(int B, const gsv_sampler* sp, hipStream_t st, in
     a.B = B;
     // layer groups: as many as the engine stream's CUs hold (all of them unless the
     // vocoder is overlapped on its own CUs)
-    a.groups = std::min(persist1_max_groups(), decode_cus() / persist1_grid(1));
+    a.groups = std::min(persist1_max_groups(), (lane ? lane1.cus : decode_cus()) / persist1_grid(1));
     if (const char* e = std::getenv("GENIE_PERSIST_GROUPS")) a.groups = std::max(3, std::min(a.groups, std::atoi(e)));
     for (int l = 0; l < 24; ++l) {
         const T2SLayerW& W = layers[l];
         a.L[l] = PLayer{W.w_in, W.w_out, W.w1, W.w2, W.b_in, W.b_out, W.b1, W.b2, W.n1w, W.n1b, W.n2w, W.n2b};
     }
     a.emb = emb_audio; a.alpha = alpha_audio; a.pe = pe_tab; a.w_pred = w_pred;
-    for (int l = 0; l < 24; ++l) { a.kc[l] = kcache[l]; a.vc[l] = vcache[l]; }
+    for (int l = 0; l < 24; ++l) { a.kc[l] = kcache[l] + slot_kv; a.vc[l] = vcache[l] + slot_kv; }
     a.sstride = (long)16 * tmax * 32; a.tmax = tmax; a.scale = qk_scale;
-    a.y = y; a.ldy = tmax; a.ny = ny; a.kvlen = kvlen; a.steps = steps; a.done = done; a.stop_out = stopf;
-    a.seen = seen;
+    a.y = y + (size_t)slot * tmax; a.ldy = tmax; a.ny = ny + slot; a.kvlen = kvlen + slot; a.steps = steps + slot;
+    a.done = done + slot; a.stop_out = stopf + slot;
+    a.seen = seen + (size_t)slot * 33;
     a.top_k = sp->top_k; a.temperature = sp->temperature; a.rep_penalty = sp->repetition_penalty;
     a.greedy = sp->greedy; a.seed = sp->seed; a.max_steps = sp->max_steps; a.force_steps = sp->force_steps;
-    a.force_b = forceb;
+    a.force_b = forceb + slot;
     a.ring = (unsigned long long*)pws;
     a.epoch = pepoch;
     a.err = perr;
@@ -1199,12 +1215,19 @@ int gsv_engine::persist_enqueue(int B, const gsv_sampler* sp, hipStream_t st, in
     if (le != hipSuccess)
         return set_error(GSV_E_HIP, "persistent decode launch");
     ++persist_launches;
+    ++lb.launches[lane];
     hipMemcpyAsync(perr_dst, perr, 4, hipMemcpyDeviceToHost, st);
-    if (res_dst) enqueue_results(res_b, st, res_dst);   // valid if this launch succeeds
+    if (res_dst) enqueue_results(res_b, st, res_dst, slot);   // valid if this launch succeeds
     // a queued overlapped vocoder call and T2S prefetch: enqueue them now (vocoder
-    // CUs, in that order), while the GPU decodes
+    // CUs, in that order), while the GPU decodes.  Two lanes: the next start, on the lane that
+    // is free by then, waits for the prefetch, but the caller waits for the vocoder call before
+    // it makes that start, so the other order (option prefetch_first) gains nothing
+    const bool pf_first = lb.lanes == 2 && prefetch_first;
+    if (pf_first)
+        if (int r = pf_launch_queued()) return r;
     if (int r = vits_launch_queued()) return r;
-    if (int r = pf_launch_queued()) return r;
+    if (!pf_first)
+        if (int r = pf_launch_queued()) return r;
     return 0;
 }
 
@@ -1320,23 +1343,25 @@ struct SlotCopyArgs {
     int* forceb;
     int force0;
     int* err;
+    int dslot;   // destination slot (0, or a lane's)
 };
 // block (head h, layer l, k|v): rows [0, n0) of the head, contiguous n0 x 32 floats
 __global__ __launch_bounds__(256) void k_slot_copy(SlotCopyArgs a) {
     const int h = blockIdx.x, l = blockIdx.y;
     float* base = (blockIdx.z ? a.vc[l] : a.kc[l]) + (long)h * a.tmax * 32;
     const float4* src = reinterpret_cast<const float4*>(base + a.sstride);
-    float4* dst = reinterpret_cast<float4*>(base);
+    float4* dst = reinterpret_cast<float4*>(base + a.dslot * a.sstride);
     for (int i = threadIdx.x; i < a.n0 * 8; i += 256) dst[i] = src[i];
     if (h == 0 && l == 0 && blockIdx.z == 0) {
-        for (int i = threadIdx.x; i < a.tmax; i += 256) a.y[i] = a.y[a.tmax + i];
-        if (threadIdx.x < 33) a.seen[threadIdx.x] = a.seen[33 + threadIdx.x];
+        const int d = a.dslot;
+        for (int i = threadIdx.x; i < a.tmax; i += 256) a.y[(long)d * a.tmax + i] = a.y[a.tmax + i];
+        if (threadIdx.x < 33) a.seen[33 * d + threadIdx.x] = a.seen[33 + threadIdx.x];
         if (threadIdx.x == 0) {
-            a.ny[0] = a.ny[1];
-            a.kvlen[0] = a.kvlen[1];
-            a.steps[0] = a.steps[1];
-            a.done[0] = a.done[1];
-            a.forceb[0] = a.force0;
+            a.ny[d] = a.ny[1];
+            a.kvlen[d] = a.kvlen[1];
+            a.steps[d] = a.steps[1];
+            a.done[d] = a.done[1];
+            a.forceb[d] = a.force0;
             if (a.err) a.err[0] = 0;
         }
     }
@@ -1370,6 +1395,7 @@ int gsv_engine::pf_launch_queued() {
     const int L = u.n_ref + u.n_text, P = u.n_ssl / 2;
     hipStreamWaitEvent(vstream, pf_in, 0);
     hipStreamWaitEvent(vstream, pf_fork, 0);   // the engine stream's encoder / prefill work (same workspaces)
+    if (ws_free_valid) hipStreamWaitEvent(vstream, ws_free, 0);   // ... and the other lane's
     if (pf_copied_valid) hipStreamWaitEvent(vstream, pf_copied, 0);   // slot 1 taken by the last generate
     if (timing) hipEventRecord(pf_ev[0], vstream);
     if (int e = encode(&u, pH, prompts_buf, vstream)) return e;
@@ -1377,6 +1403,7 @@ int gsv_engine::pf_launch_queued() {
     if (int e = prefill_slot(1, pH, L, prompts_buf, P, &pf_p.sp, nullptr, vstream, 0)) return e;
     if (timing) hipEventRecord(pf_ev[2], vstream);
     hipEventRecord(pf_done, vstream);
+    pf_done_valid = true;
     pf_pending = true;
     return 0;
 }
@@ -1392,14 +1419,15 @@ int gsv_engine::pf_drop(bool keep_queued) {
 
 // Also sets slot 0's forced step count and zeroes the decode error word (two
 // stream operations fewer before the decode launch).
-void gsv_engine::pf_take(hipStream_t st, int force0) {
+void gsv_engine::pf_take(hipStream_t st, int force0, int lane) {
     hipStreamWaitEvent(st, pf_done, 0);
+    int*& perr = lane ? lane1.err : this->perr;
     if (!perr && hipMalloc((void**)&perr, 64) != hipSuccess) perr = nullptr;
     SlotCopyArgs a{};
     for (int l = 0; l < 24; ++l) { a.kc[l] = kcache[l]; a.vc[l] = vcache[l]; }
     a.sstride = (long)16 * tmax * 32; a.tmax = tmax; a.n0 = pf_p.n0;
     a.y = y; a.ny = ny; a.kvlen = kvlen; a.steps = steps; a.done = done; a.seen = seen;
-    a.forceb = forceb; a.force0 = force0; a.err = perr;
+    a.forceb = forceb; a.force0 = force0; a.err = perr; a.dslot = LaneBook::slot_of(lane);
     perr_zeroed = perr != nullptr;
     hipLaunchKernelGGL(k_slot_copy, dim3(16, 24, 2), dim3(256), 0, st, a);
     hipEventRecord(pf_copied, st);
@@ -1436,11 +1464,11 @@ int gsv_engine::ensure_res_pin(int batch) {
 }
 
 // [ny: batch int][steps: batch int][y: batch x tmax int64] -> dst (pinned)
-void gsv_engine::enqueue_results(int batch, hipStream_t st, char* dst) {
+void gsv_engine::enqueue_results(int batch, hipStream_t st, char* dst, int slot) {
     int* h = reinterpret_cast<int*>(dst);
-    hipMemcpyAsync(h, ny, (size_t)batch * 4, hipMemcpyDeviceToHost, st);
-    hipMemcpyAsync(h + batch, steps, (size_t)batch * 4, hipMemcpyDeviceToHost, st);
-    hipMemcpyAsync(dst + (size_t)batch * 8, y, (size_t)batch * tmax * 8, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(h, ny + slot, (size_t)batch * 4, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(h + batch, steps + slot, (size_t)batch * 4, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(dst + (size_t)batch * 8, y + (size_t)slot * tmax, (size_t)batch * tmax * 8, hipMemcpyDeviceToHost, st);
 }
 
 // Inference.py:108-109 then :41-44 on the copied results: y[:, -idx:] with the last
@@ -1728,12 +1756,15 @@ extern "C" int gsv_t2s_generate(gsv_engine* eng, int batch, const gsv_utt* utts,
 
 // ============================================================ asynchronous generate
 int gsv_engine::gen_drain() {
-    if (gq_n == 0) return 0;
-    return hipStreamSynchronize(stream) == hipSuccess ? 0 : set_error(GSV_E_HIP, "generate drain");
+    if (lb.empty()) return 0;
+    for (hipStream_t s : {stream, lane1.st})
+        if (s && hipStreamSynchronize(s) != hipSuccess) return set_error(GSV_E_HIP, "generate drain");
+    lb.drained();
+    return 0;
 }
 
 int gsv_engine::gen_start(const gsv_utt& u, const gsv_sampler& sp, hipStream_t caller) {
-    if (gq_n == 2) return set_error(GSV_E_STATE, "two generates in flight: finish one first");
+    if (lb.full()) return set_error(GSV_E_STATE, "two generates in flight: finish one first");
     if (u.force_steps < 0) return set_error(GSV_E_ARG, "negative force_steps");
     const int L = u.n_ref + u.n_text, P = u.n_ssl / 2;
     if (L <= 0 || P <= 0) return set_error(GSV_E_ARG, "empty utterance");
@@ -1742,12 +1773,13 @@ int gsv_engine::gen_start(const gsv_utt& u, const gsv_sampler& sp, hipStream_t c
     const bool hit = pf_pending && same_utt(u, pf_p.u) && same_sampler(sp, pf_p.sp);
     if (!hit)
         if (int e = pf_drop(true)) return e;
-    if (need > tmax || max_batch < 1) {   // the KV cache is re-allocated: nothing may be in flight
+    const int want = lb.slots(false);   // two lanes: their slots and the prefetch slot between them
+    if (need > tmax || max_batch < want) {   // the KV cache is re-allocated: nothing may be in flight (either lane)
         if (int e = gen_drain()) return e;
         if (int e = pf_drop()) return e;
     }
-    if (int e = reserve(1, need)) return e;
-    GenSlot& g = gq[(gq_head + gq_n) % 2];
+    if (int e = reserve(want, need)) return e;
+    GenSlot& g = gq[lb.tail()];
     const size_t rb = 8 + (size_t)tmax * 8;
     if (g.res_bytes < rb) {
         retire_host(g.res);
@@ -1766,26 +1798,44 @@ int gsv_engine::gen_start(const gsv_utt& u, const gsv_sampler& sp, hipStream_t c
     g.hit = hit;
     g.sync = false;
     g.sync_rc = 0;
-    hipStream_t st = stream;
+    const bool persist_ok = use_persist && use_persist1 && decode_cus() >= persist1_grid(3) && !stop_requested() &&
+                            persist_admit();
+    // the lane whose previous generate was started least recently (the one not in use); the
+    // per-step graphs of the other path decode on slot 0, the engine stream
+    const int lane = persist_ok ? lb.next_lane() : 0;
+    const int slot = LaneBook::slot_of(lane);
+    hipStream_t st = lane ? lane1.st : stream;
     hipEventRecord(ev_in, caller);   // the caller's inputs are ready here; its stream is NOT made to
     hipStreamWaitEvent(st, ev_in, 0);   // wait for the engine (gen_finish orders it)
     loop_limit = cap;
     if (hit) {
-        pf_take(st, u.force_steps);
+        pf_take(st, u.force_steps, lane);
     } else {
-        hipMemsetD32Async(forceb, u.force_steps, 1, st);
-        hipMemsetAsync(done, 1, max_batch, st);
+        hipMemsetD32Async(forceb + slot, u.force_steps, 1, st);
+        if (lb.lanes == 2) {
+            // the other lane's slot may be decoding; and the shared encoder / prefill workspaces
+            // are free once the other lane's prefill and the last launched prefetch are done
+            hipMemsetAsync(done + slot, 1, 1, st);
+            if (ws_free_valid) hipStreamWaitEvent(st, ws_free, 0);
+            if (pf_done_valid) hipStreamWaitEvent(st, pf_done, 0);
+        } else {
+            hipMemsetAsync(done, 1, max_batch, st);
+        }
         if (timing) hipEventRecord(ev[0], st);
         if (int e = encode(&u, pH, prompts_buf, st)) return e;
         if (timing) hipEventRecord(ev[1], st);
-        if (int e = prefill_slot(0, pH, L, prompts_buf, P, &sp, nullptr, st)) return e;
+        if (int e = prefill_slot(slot, pH, L, prompts_buf, P, &sp, nullptr, st, 0)) return e;
+        if (lb.lanes == 2) {
+            if (!ws_free && hipEventCreateWithFlags(&ws_free, hipEventDisableTiming) != hipSuccess)
+                return set_error(GSV_E_HIP, "workspace event");
+            hipEventRecord(ws_free, st);
+            ws_free_valid = true;
+        }
     }
     hipEventRecord(g.d0, st);
-    const bool persist_ok = use_persist && use_persist1 && decode_cus() >= persist1_grid(3) && !stop_requested() &&
-                            persist_admit();
     int rc = 0;
     if (persist_ok) {
-        rc = persist_enqueue(1, &sp, st, g.perr_h, timing ? g.k0 : nullptr, timing ? g.k1 : nullptr, g.res, 1);
+        rc = persist_enqueue(1, &sp, st, g.perr_h, timing ? g.k0 : nullptr, timing ? g.k1 : nullptr, g.res, 1, lane);
     } else {   // no persistent path (or a stop is pending): this one runs to completion now
         res_batch = 1;
         res_ready = false;
@@ -1800,20 +1850,18 @@ int gsv_engine::gen_start(const gsv_utt& u, const gsv_sampler& sp, hipStream_t c
     loop_limit = 0;
     if (rc && !g.sync) return rc;
     hipEventRecord(g.done, st);
-    ++gq_n;
+    lb.push(lane);
     return 0;
 }
 
 int gsv_engine::gen_finish(int64_t* out_tokens, int out_stride, int32_t* out_len, hipStream_t caller) {
-    if (gq_n == 0) return set_error(GSV_E_STATE, "no generate in flight");
+    if (lb.empty()) return set_error(GSV_E_STATE, "no generate in flight");
     // A vocoder call still queued here had no later generate to launch it behind (the
     // last sentences of a stream): launch it on the vocoder CUs now, beside the decode
     // this call waits for, instead of after it on the T2S CUs.
     if (vqueued && vstream)
         if (int r = vits_launch_queued(vstream)) return r;
-    GenSlot& g = gq[gq_head];
-    gq_head = (gq_head + 1) % 2;
-    --gq_n;
+    GenSlot& g = gq[lb.pop()];
     if (g.sync && g.sync_rc) return g.sync_rc == GSV_E_STOPPED ? set_error(GSV_E_STOPPED, "stopped by gsv_request_stop")
                                                                : g.sync_rc;
     for (;;) {   // poll, as host_wait
@@ -1832,20 +1880,26 @@ int gsv_engine::gen_finish(int64_t* out_tokens, int out_stride, int32_t* out_len
         if (*g.perr_h == 2) ++persist1_f16_reruns;
         else if (*g.perr_h == 1) note_persist_timeout();
         if (int e = gen_drain()) return e;
-        const int saved_n = gq_n;
-        gq_n = 0;   // the synchronous path must not see the queue
+        // (both lanes drained: the other started generate's results and error word are in its
+        // pinned buffers already, so the re-run may take slot 0 whichever lane that one ran on)
+        const int saved_n = lb.hide();   // the synchronous path must not see the queue
         const int r = gsv_t2s_generate(this, 1, &g.u, &g.sp, out_tokens, out_stride, out_len, caller);
-        gq_n = saved_n;
+        lb.unhide(saved_n);
         return r;
     }
     if (timing) {
+        // the encode / prefill events are the engine's, not the generate's: with two lanes a later
+        // prefetch or the other lane's prefill may have re-recorded them and still be running
+        // (hipErrorNotReady: the phase keeps its last value, and the error is not left pending)
+        hipError_t te = hipSuccess;
         if (g.hit) {
-            hipEventElapsedTime(&ms[0], pf_ev[0], pf_ev[1]);
-            hipEventElapsedTime(&ms[1], pf_ev[1], pf_ev[2]);
+            te = hipEventElapsedTime(&ms[0], pf_ev[0], pf_ev[1]);
+            if (te == hipSuccess) te = hipEventElapsedTime(&ms[1], pf_ev[1], pf_ev[2]);
         } else {
-            hipEventElapsedTime(&ms[0], ev[0], ev[1]);
-            hipEventElapsedTime(&ms[1], ev[1], g.d0);
+            te = hipEventElapsedTime(&ms[0], ev[0], ev[1]);
+            if (te == hipSuccess) te = hipEventElapsedTime(&ms[1], ev[1], g.d0);
         }
+        if (te != hipSuccess) (void)hipGetLastError();
         hipEventElapsedTime(&ms[2], g.d0, g.done);
         if (!g.sync) probe_sample(g.k0, g.k1);
     }
@@ -1884,9 +1938,12 @@ extern "C" int gsv_t2s_prefetch(gsv_engine* eng, const gsv_utt* utt, const gsv_s
     if (int e = norm_sampler(s, sp)) return e;
     const int cap = utt->force_steps > 0 ? utt->force_steps : sp.force_steps > 0 ? sp.force_steps : sp.max_steps;
     const int need = L + P + cap + 16;
-    if (eng->max_batch < 2 || need > eng->tmax)   // the KV cache is re-allocated: nothing may be in flight
+    const int want = eng->lb.slots(true);
+    if (eng->max_batch < want || need > eng->tmax) {   // the KV cache is re-allocated: nothing may be in flight
+        if (int e = eng->gen_drain()) return e;
         if (int e = eng->pf_drop()) return e;
-    if (int e = eng->reserve(2, need)) return e;
+    }
+    if (int e = eng->reserve(want, need)) return e;
     if (!eng->pf_in) {
         for (hipEvent_t* e : {&eng->pf_in, &eng->pf_done, &eng->pf_copied, &eng->pf_fork})
             if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return set_error(GSV_E_HIP, "prefetch events");
@@ -2020,7 +2077,7 @@ extern "C" int gsv_set_option(gsv_engine* eng, const char* name, int value) {
             eng->lane_priority = p;
             if (int r = eng->remake_lane_streams()) return r;
         } else {
-            if (eng->vocoder_cus || eng->gq_n || !eng->own_stream)
+            if (eng->vocoder_cus || eng->lb.n || !eng->own_stream)
                 return set_error(GSV_E_STATE, "t2s_priority: needs the engine's own unmasked stream, idle");
             if (int r = eng->pf_drop()) return r;
             hipStream_t ns = nullptr;
@@ -2051,6 +2108,17 @@ extern "C" int gsv_set_option(gsv_engine* eng, const char* name, int value) {
                 eng->dec_cu_off = save_o;
                 return r;
             }
+    } else if (n == "decode_lanes") {   // 1: one decode lane under vocoder_cus (2, the default: two wherever they fit)
+        if (value < 1 || value > 2) return set_error(GSV_E_ARG, "decode_lanes: 1 or 2");
+        const int save = eng->decode_lanes_opt;
+        eng->decode_lanes_opt = value;
+        if (eng->vocoder_cus)
+            if (int r = eng->set_vocoder_cus(eng->vocoder_cus)) {
+                eng->decode_lanes_opt = save;
+                return r;
+            }
+    } else if (n == "prefetch_first") {   // two lanes: the vocoder stream's order (see persist_enqueue)
+        eng->prefetch_first = value != 0;
     } else if (n == "vocoder_cus") {   // overlapped vocoder: CUs reserved for gsv_vits_decode_async
         return eng->set_vocoder_cus(value);
     } else if (n == "sv_f16") {   // speaker verification on the split-fp16 MFMA convs (0: the f32 MFMA path)
@@ -2098,6 +2166,9 @@ extern "C" int gsv_get_counter(gsv_engine* eng, const char* name, int64_t* value
     else if (n == "w16_split_tensors") *value = eng->w16_split_tensors;
     else if (n == "persist_disabled") *value = eng->persist_disabled;
     else if (n == "persist_launches") *value = eng->persist_launches;
+    else if (n == "decode_lanes") *value = eng->decode_lanes();
+    else if (n == "lane_launches_0") *value = eng->lb.launches[0];
+    else if (n == "lane_launches_1") *value = eng->lb.launches[1];
     else if (n == "persist_hold") *value = eng->persist_hold;
     else if (n == "stops") *value = eng->stops;
     else if (n == "graph_fallbacks") *value = eng->graph_fallbacks;

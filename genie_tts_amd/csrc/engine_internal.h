@@ -14,6 +14,7 @@
 
 #include "../../include/genie_engine.h"
 #include "kernels.h"
+#include "lanes.h"
 #include "vits.h"
 
 namespace gsv {
@@ -305,10 +306,10 @@ struct gsv_engine {
     int res_batch = 0;                 // > 0: decode_persistent_as enqueues the copies
     bool res_ready = false;            // they were enqueued behind the final decode and synced
     int ensure_res_pin(int batch);
-    void enqueue_results(int batch, hipStream_t st, char* dst);
+    void enqueue_results(int batch, hipStream_t st, char* dst, int slot = 0);
     int trim_results(const char* res, int batch, int64_t* out_tokens, int out_stride, int32_t* out_len);
     int persist_enqueue(int B, const gsv_sampler* sp, hipStream_t st, int* perr_dst, hipEvent_t k0,
-                        hipEvent_t k1, char* res_dst, int res_b);
+                        hipEvent_t k1, char* res_dst, int res_b, int lane = 0);
     void probe_sample(hipEvent_t k0, hipEvent_t k1);
     // asynchronous single-utterance generate (gsv_t2s_generate_start / _finish): up to
     // two in flight on the engine stream, so the next decode is queued behind the
@@ -324,7 +325,33 @@ struct gsv_engine {
         int sync_rc = 0;
     };
     GenSlot gq[2];
-    int gq_head = 0, gq_n = 0;
+    gsv::LaneBook lb;                  // FIFO of gq, lane of each started generate (lanes.h)
+    // Decode lanes (option "decode_lanes", default 2): under option vocoder_cus with >= 192 decode
+    // CUs two started generates decode side by side, each on a CU-masked stream over its own
+    // multiple of 32 of the decode CUs, with a KV / sequence-state slot, hand-off ring, epoch and
+    // error word of its own.  Lane 0 is the engine stream with pws / pepoch / perr and slot 0 (what
+    // every synchronous path uses); lane 1 is this.  One lane: as before, the second start queued
+    // behind the first on the engine stream.
+    struct DecodeLane {
+        hipStream_t st = nullptr;
+        int cus = 0;
+        void* ring = nullptr;
+        size_t ring_bytes = 0;
+        unsigned epoch = 0;
+        int* err = nullptr;
+    } lane1;
+    int decode_lanes_opt = 2;
+    int lane0_cus = 0;                 // two lanes: CUs of the engine stream (lane 0)
+    int decode_lanes() const { return lb.lanes; }
+    // the encoder / prefill workspaces (pH, prompts_buf, ...) are shared: a lane's own prefill (a
+    // start that missed the prefetch) is ordered after the other lane's and the prefetch's by events
+    hipEvent_t ws_free = nullptr;      // after the latest encode + prefill issued on a lane stream
+    bool ws_free_valid = false, pf_done_valid = false;
+    // option "prefetch_first": two lanes -- the queued prefetch before the queued vocoder call on the
+    // vocoder stream.  Off: the caller waits for the vocoder call (gsv_vits_wait) before its next
+    // start, so the stream's period is vocoder + prefill in either order (8.47 vs 8.49 ms per
+    // utterance, profiles/decode_lanes_vocoder_order_ab.txt)
+    bool prefetch_first = false;
     int gen_start(const gsv_utt& u, const gsv_sampler& sp, hipStream_t caller);
     int gen_finish(int64_t* out_tokens, int out_stride, int32_t* out_len, hipStream_t caller);
     int gen_drain();                   // wait for every started generate (their results stay queued)
@@ -464,9 +491,11 @@ struct gsv_engine {
     // (options "decode_cus" / "decode_cu_offset": several engines, e.g. one per process, can
     // share the vocoder CUs [0, K) while each decodes on CUs of its own)
     int dec_cus_opt = 0, dec_cu_off = 0;
-    int decode_cus() const {
+    // Two lanes: the engine stream's share (lane 0), which every grid launched on it is sized for.
+    int decode_cus_all() const {
         return vocoder_cus == 0 ? n_cu : dec_cus_opt > 0 ? dec_cus_opt : n_cu - vocoder_cus - dec_cu_off;
     }
+    int decode_cus() const { return lb.lanes == 2 ? lane0_cus : decode_cus_all(); }
     // T2S prefetch (gsv_t2s_prefetch): encode + prefill of the next utterance into
     // slot 1 on the vocoder CUs while slot 0 decodes; taken into slot 0 by the
     // generate it was made for
@@ -483,7 +512,7 @@ struct gsv_engine {
     hipEvent_t pf_ev[3] = {};          // timing: encode, prefill, end (vocoder stream)
     int pf_launch_queued();
     int pf_drop(bool keep_queued = false);
-    void pf_take(hipStream_t st, int force0);
+    void pf_take(hipStream_t st, int force0, int lane = 0);
     bool perr_zeroed = false;          // the next persistent launch's error word was zeroed by pf_take
     bool spin_wait = true;             // option "spin_wait"
     hipError_t host_wait(hipStream_t st);

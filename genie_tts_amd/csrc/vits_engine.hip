@@ -569,13 +569,14 @@ int gsv_engine::stream_cus(hipStream_t st) const {
     if (vocoder_cus == 0) return n_cu;
     if (st == vstream) return vocoder_cus;
     if (st == stream) return decode_cus();
+    if (st && st == lane1.st) return lane1.cus;
     for (const VitsLane& L : vlanes)
         if (st == L.st) return lanes_all_cus ? n_cu : vocoder_cus;
     return n_cu;
 }
 
 gsv_engine::SideStream* gsv_engine::side_of(hipStream_t s) {
-    bool own = s && (s == stream || s == vstream);
+    bool own = s && (s == stream || s == vstream || s == lane1.st);
     for (const VitsLane& L : vlanes) own = own || s == L.st;
     if (!own) return nullptr;   // a caller's stream: its lifetime is not the engine's to track
     std::lock_guard<std::mutex> lk(side_mu);
@@ -641,12 +642,16 @@ int gsv_engine::set_vocoder_cus(int K) {
     if (K != 0 && (dec_cu_off % 8 != 0 || D % 32 != 0 || D < 3 * persist1_grid(1) || K + dec_cu_off + D > n_cu))
         return set_error(GSV_E_ARG, "decode_cus / decode_cu_offset: a multiple of 32 (>= 96) CUs at a multiple "
                                     "of 8 past the vocoder CUs, within the chip");
-    if (gq_n) return set_error(GSV_E_STATE, "vocoder_cus: finish the started generates first");
+    if (lb.n) return set_error(GSV_E_STATE, "vocoder_cus: finish the started generates first");
     if (int r = vits_wait(nullptr)) return r;
     if (int r = vits_batch_finish(nullptr)) return r;
     if (int r = pf_drop()) return r;   // a launched prefetch runs on the vocoder stream
     if (sync_own_streams() != hipSuccess) return set_error(GSV_E_HIP, "vocoder_cus sync");
-    hipStream_t ns = nullptr, nv = nullptr;
+    // two decode lanes where they fit: the decode CUs split into two multiples of 32, each >= 96
+    // (192 -> 96 + 96, 224 -> 128 + 96); lane 0 stays the engine stream
+    const int L1 = K != 0 && decode_lanes_opt >= 2 && D >= 2 * 3 * persist1_grid(1) ? D / 2 / 32 * 32 : 0;
+    const int L0 = D - L1;
+    hipStream_t ns = nullptr, nv = nullptr, nl = nullptr;
     if (K == 0) {
         if (hipStreamCreateWithFlags(&ns, hipStreamNonBlocking) != hipSuccess) return set_error(GSV_E_HIP, "stream");
     } else {
@@ -654,7 +659,13 @@ int gsv_engine::set_vocoder_cus(int K) {
         std::vector<uint32_t> mt(words, 0u), mv(words, 0u);
         for (int i = 0; i < n_cu; ++i) {
             if (i < K) mv[i / 32] |= 1u << (i % 32);
-            else if (i >= K + dec_cu_off && i < K + dec_cu_off + D) mt[i / 32] |= 1u << (i % 32);
+            else if (i >= K + dec_cu_off && i < K + dec_cu_off + L0) mt[i / 32] |= 1u << (i % 32);
+        }
+        if (L1) {
+            std::vector<uint32_t> ml(words, 0u);
+            for (int i = K + dec_cu_off + L0; i < K + dec_cu_off + D; ++i) ml[i / 32] |= 1u << (i % 32);
+            if (hipExtStreamCreateWithCUMask(&nl, (uint32_t)words, ml.data()) != hipSuccess)
+                return set_error(GSV_E_HIP, "CU-masked stream");
         }
         if (hipExtStreamCreateWithCUMask(&ns, (uint32_t)words, mt.data()) != hipSuccess ||
             hipExtStreamCreateWithCUMask(&nv, (uint32_t)words, mv.data()) != hipSuccess)
@@ -666,9 +677,15 @@ int gsv_engine::set_vocoder_cus(int K) {
     drop_sides();
     if (own_stream && stream) hipStreamDestroy(stream);
     if (vstream) hipStreamDestroy(vstream);
+    if (lane1.st) hipStreamDestroy(lane1.st);
     stream = ns;
     own_stream = true;
     vstream = nv;
+    lane1.st = nl;
+    lane1.cus = L1;
+    lane0_cus = L0;
+    lb.configure(nl ? 2 : 1);
+    ws_free_valid = false;
     vocoder_cus = K;
     return remake_lane_streams();
 }
@@ -715,7 +732,7 @@ int gsv_engine::vits_launch_queued(hipStream_t s) {
 int gsv_engine::vits_wait(hipStream_t caller) {
     // still queued (no decode launched since): nothing runs on the engine stream unless
     // a started generate does, so the call takes the T2S CUs
-    if (int r = vits_launch_queued(gq_n == 0 ? stream : vstream)) return r;
+    if (int r = vits_launch_queued(lb.n == 0 ? stream : vstream)) return r;
     if (!vpending) return 0;
     vpending = false;
     if (hipEventSynchronize(vev_done) != hipSuccess) return set_error(GSV_E_HIP, "overlapped vocoder");

@@ -407,7 +407,8 @@ class Engine:
 
     def t2s_generate_start(self, utt: Tuple, sampler: Optional[Sampler] = None):
         """Queue the T2S of one utterance (gsv_t2s_generate_start) and return at once;
-        up to two in flight, so the next decode is queued behind the running one.
+        up to two in flight: on two decode lanes side by side where the CU split leaves >= 192
+        decode CUs (option decode_lanes), else the next decode queued behind the running one.
         t2s_generate_finish() returns the oldest one's tokens."""
         pf = getattr(self, "_pf", [])
         hit = next((j for j, p in enumerate(pf) if p[0] is utt), None)
@@ -674,13 +675,15 @@ class Engine:
         return us.value, n.value
 
     def set_option(self, name: str, value: int):
-        """Engine option (see gsv_set_option): "persist" decode path, "ptrace" phase stamps."""
+        """Engine option (see gsv_set_option): "persist" decode path, "ptrace" phase stamps,
+        "decode_lanes" (1: started generates one behind the other instead of on two lanes)."""
         _check(lib().gsv_set_option(self.h, name.encode(), int(value)), "gsv_set_option")
 
     def counter(self, name: str) -> int:
         """Engine counter (gsv_get_counter): persist_timeouts, persist1_f16_reruns, vits_f32_reruns,
         sv_f32_reruns, w16_split_tensors, persist_disabled (timeout back-off holds begun),
-        persist_launches, persist_hold (generates left in the current hold), stops, graph_fallbacks,
+        persist_launches, decode_lanes (1 or 2, as configured), lane_launches_0 / lane_launches_1
+        (persistent launches per decode lane), persist_hold (generates left in the current hold), stops, graph_fallbacks,
         retired_bytes (replaced device buffers not yet freed), reclaimed_bytes, reclaims."""
         v = ctypes.c_int64()
         _check(lib().gsv_get_counter(self.h, name.encode(), ctypes.byref(v)), "gsv_get_counter")

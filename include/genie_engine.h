@@ -239,7 +239,21 @@ int gsv_t2s_prefetch(gsv_engine* eng, const gsv_utt* utt, const gsv_sampler* sam
  * started one and returns its trimmed tokens (host [out_stride]) as
  * gsv_t2s_generate would, ordering `stream` after it.  A launch that meets the
  * fp16-range or hand-off-timeout condition is re-run synchronously inside _finish.
- * Other T2S calls wait for the started ones first; their results stay queued. */
+ * Other T2S calls wait for the started ones first; their results stay queued.
+ *
+ * Decode lanes.  Under option "vocoder_cus" with at least 192 decode CUs (and option
+ * "decode_lanes" at its default 2) the engine owns two decode lanes: CU-masked streams over
+ * disjoint multiples of 32 of the decode CUs (192 -> 96 + 96, 224 -> 128 + 96), each with a
+ * KV / sequence-state slot, hand-off ring and error word of its own.  A _start then takes
+ * the lane whose previous generate was started least recently, so it may RUN BESIDE the
+ * previous started generate instead of behind it: the sentences of a stream must be
+ * independent (they are in the reference), and the utt's buffers of both must stay valid
+ * until their _finish.  _finish still returns the results in the order of the starts.
+ * The tokens are those of gsv_t2s_generate on either lane.  With fewer decode CUs, or
+ * "decode_lanes" 1, there is one lane and a second start is queued behind the first.
+ * Under two lanes the engine stream -- every synchronous or batched call under
+ * "vocoder_cus" -- runs on lane 0's CUs only; a caller who mixes such calls into the
+ * split and wants all decode CUs for them sets "decode_lanes" 1. */
 int gsv_t2s_generate_start(gsv_engine* eng, const gsv_utt* utt, const gsv_sampler* sampler, void* stream);
 int gsv_t2s_generate_finish(gsv_engine* eng, int64_t* out_tokens, int32_t out_stride, int32_t* out_len,
                             void* stream);
@@ -366,6 +380,10 @@ int gsv_request_stop(gsv_engine* eng, int32_t on);
  * sequences per 16 CUs).  "persist_backoff" / "persist_backoff_ms": the first back-off hold
  * after two timed-out launches in a row (64 generates / 5 s, doubling per failed re-probe).
  * "vocoder_cus" (CU split for the sentence pipeline), "decode_cus" / "decode_cu_offset",
+ * "decode_lanes" (2, default: two decode lanes under "vocoder_cus" wherever >= 192 decode CUs
+ * hold them, see gsv_t2s_generate_start; 1: one lane, a second started generate queued behind
+ * the first; set with no generate started), "prefetch_first" (0, default; 1: with two lanes a
+ * queued prefetch is launched before the queued vocoder call -- measured equal),
  * "vits_lanes", "seg_vocoder" (1, default: a vocoder batch runs its generator as ONE pass
  * over all utterances laid out back to back), "seg_front" (1, default: its text/flow part
  * too, see gsv_vits_decode_batch), "convh" (MRF convs on the split-fp16 MFMA),
@@ -393,7 +411,9 @@ int gsv_set_option(gsv_engine* eng, const char* name, int value);
 /* Engine counters: "persist_timeouts" (persistent decode launches whose hand-offs
  * timed out -- e.g. other work on the device -- and re-ran as per-step graphs),
  * "persist_disabled" (back-off holds begun), "persist_hold" (generates left in the
- * current hold), "persist_launches", "persist1_f16_reruns" (fp16-range fallbacks),
+ * current hold), "persist_launches", "decode_lanes" (1 or 2: the decode lanes as currently
+ * configured), "lane_launches_0" / "lane_launches_1" (persistent launches issued on each
+ * lane; the synchronous paths count on lane 0), "persist1_f16_reruns" (fp16-range fallbacks),
  * "vits_f32_reruns", "vits_packed_fronts" (vocoder batches whose text/flow part ran
  * packed), "sv_f32_reruns", "w16_split_tensors" (fp32 weights kept as hi + lo
  * planes), "stops" (generates abandoned by gsv_request_stop), "graph_fallbacks"
