@@ -28,6 +28,7 @@ sounddevice fails (Core/TTSPlayer.py:136-146).
 from __future__ import annotations
 
 import asyncio
+import functools
 import logging
 import os
 import threading
@@ -232,7 +233,15 @@ def _ensure_sv_emb(m, ref) -> None:
         ref.sv_emb = np.asarray(sv, np.float32).reshape(1, -1)
 
 
-def _synthesize(character_name: str, sentence, text_bert=None, sampler=None) -> np.ndarray:
+def _rate(speed) -> dict:
+    """The speech-rate keyword of a synthesis call: nothing at 1.0 (today's call, unchanged),
+    ValueError for a rate the engine rejects (outside 0.25 .. 4, not finite)."""
+    from .engine import vits_frames
+    vits_frames(0, speed)
+    return {} if float(speed) == 1.0 else {"speed": float(speed)}
+
+
+def _synthesize(character_name: str, sentence, text_bert=None, sampler=None, speed: float = 1.0) -> np.ndarray:
     m = model_manager.get(character_name)
     if m is None:
         raise ValueError(f"character '{character_name}' is not loaded")
@@ -245,14 +254,15 @@ def _synthesize(character_name: str, sentence, text_bert=None, sampler=None) -> 
         tts_client.stop_event.set()
         return None
     return tts_client.tts(sentence, ref, m.T2S_ENCODER, m.T2S_FIRST_STAGE_DECODER, m.T2S_STAGE_DECODER, m.VITS,
-                          m.PROMPT_ENCODER, m.LANGUAGE, text_bert=text_bert, g2p=_g2p, sampler=sampler)
+                          m.PROMPT_ENCODER, m.LANGUAGE, text_bert=text_bert, g2p=_g2p, sampler=sampler,
+                          **_rate(speed))
 
 
-def _synthesize_all(character_name: str, sentences: List, text_bert=None, sampler=None):
+def _synthesize_all(character_name: str, sentences: List, text_bert=None, sampler=None, speed: float = 1.0):
     """Every sentence, in order; on the engine the vocoder of one sentence overlaps the
     T2S of the next (GENIE.tts_stream)."""
     if len(sentences) < 2:
-        return [_synthesize(character_name, s, text_bert, sampler) for s in sentences]
+        return [_synthesize(character_name, s, text_bert, sampler, **_rate(speed)) for s in sentences]
     m = model_manager.get(character_name)
     if m is None:
         raise ValueError(f"character '{character_name}' is not loaded")
@@ -266,7 +276,7 @@ def _synthesize_all(character_name: str, sentences: List, text_bert=None, sample
         return []
     return list(tts_client.tts_stream(sentences, ref, m.T2S_ENCODER, m.T2S_FIRST_STAGE_DECODER, m.T2S_STAGE_DECODER,
                                       m.VITS, m.PROMPT_ENCODER, m.LANGUAGE, text_bert=text_bert, g2p=_g2p,
-                                      sampler=sampler, vocoder_cus=VOCODER_CUS))
+                                      sampler=sampler, vocoder_cus=VOCODER_CUS, **_rate(speed)))
 
 
 def _play(audio: np.ndarray) -> None:
@@ -280,14 +290,18 @@ def _play(audio: np.ndarray) -> None:
 
 def tts(character_name: str, text: Union[str, Sequence[int], np.ndarray], play: bool = False,
         split_sentence: bool = True, save_path: Union[str, os.PathLike, None] = None,
-        text_bert: Optional[np.ndarray] = None, sampler=None) -> Optional[np.ndarray]:
+        text_bert: Optional[np.ndarray] = None, sampler=None, speed: float = 1.0) -> Optional[np.ndarray]:
     """Internal.py:265-310 (TTSPlayer session: split, synthesize each sentence, save the
-    concatenation as 16-bit WAV).  Returns the audio f32 [sum 1280*G_i] at 32 kHz."""
+    concatenation as 16-bit WAV).  Returns the audio f32 [sum 1280*G_i] at 32 kHz.
+    speed: the speech rate (GPT-SoVITS's `speed`, 0.25 .. 4; ValueError otherwise): sentence i
+    is 640 * Engine.vits_frames(G_i, speed) samples, its pitch unchanged."""
+    rate = _rate(speed)
     if character_name not in _reference_audios:
         logger.error("Please call 'set_reference_audio' first to set the reference audio.")
         return None
     _session_stop.clear()                    # TTSPlayer.start_session
-    chunks = [c for c in _synthesize_all(character_name, _sentences(text, split_sentence), text_bert, sampler)
+    chunks = [c for c in _synthesize_all(character_name, _sentences(text, split_sentence), text_bert, sampler,
+                                         **rate)
               if c is not None]
     audio = np.concatenate(chunks) if chunks else np.zeros(0, np.float32)
     if _session_stop.is_set():               # stopped: the session's STREAM_END (and its save) never runs
@@ -300,9 +314,11 @@ def tts(character_name: str, text: Union[str, Sequence[int], np.ndarray], play: 
 
 
 async def tts_async(character_name: str, text: str, play: bool = False, split_sentence: bool = False,
-                    save_path: Union[str, os.PathLike, None] = None) -> AsyncIterator[bytes]:
+                    save_path: Union[str, os.PathLike, None] = None, speed: float = 1.0) -> AsyncIterator[bytes]:
     """Internal.py:193-262: yields one raw 16-bit PCM chunk per sentence as soon as it
-    is synthesized (TTSPlayer chunk callback), the engine running off the event loop."""
+    is synthesized (TTSPlayer chunk callback), the engine running off the event loop.
+    speed: as for tts."""
+    rate = _rate(speed)
     if character_name not in _reference_audios:
         raise ValueError("Please call 'set_reference_audio' first to set the reference audio.")
     loop = asyncio.get_running_loop()
@@ -311,7 +327,7 @@ async def tts_async(character_name: str, text: str, play: bool = False, split_se
     for s in _sentences(text, split_sentence):
         if _session_stop.is_set():
             return
-        audio = await loop.run_in_executor(None, _synthesize, character_name, s)
+        audio = await loop.run_in_executor(None, functools.partial(_synthesize, character_name, s, **rate))
         if _session_stop.is_set():
             # stop() during the sentence: the reference's worker sends chunk_callback(None) and
             # the iterator ends without that chunk (TTSPlayer.py:109-114, Internal.py:258-262)

@@ -61,6 +61,10 @@ struct HubertWeights {
     size_t ws_floats = 0;
 };
 int hubert_frames(int n_samples);
+// Frames the vocoder runs at after the speech-rate resample (gsv_vits_frames): 2 n_sem at speed
+// 0 or 1, else (int)(2 n_sem / (double)speed) + 1; GSV_E_ARG outside [0.25, 4] or not finite.
+int vits_frames(int n_sem, float speed);
+constexpr int VITS_MAXT_OUT = 2 * MHA_MAXK_HOST;   // resampled frames the generator workspace is grown to
 // RoBERTa (bert.hip): chinese-roberta-wwm-ext-large, transformers BertModel layout
 using BertLayerW = HubertLayerW;
 struct BertWeights {
@@ -361,13 +365,16 @@ struct gsv_engine {
     // refill; 0: 4 was 0.2 % faster alone but equal in the pipelined stream (profiles/r06k_headline_ab.txt)
     int persist1_pf_delay = 0;
     int persist1_knob[4] = {0, 0, 0, 0};   // options "knob0".."knob3": single-sequence kernel tuning variants
+    // speed: the item's speech rate (0 == 1: no resample); the pass runs proj, the flows and the
+    // generator at vits_frames(n_sem, speed) frames
     int vits_decode(const int64_t* text_seq, int n_text, const int64_t* sem, int n_sem,
                     const float* ref_audio, int n_audio, const float* ge, const float* ge_adv,
-                    const float* eps, uint64_t noise_seed, float noise_scale, float* audio, hipStream_t st);
+                    const float* eps, uint64_t noise_seed, float noise_scale, float* audio, hipStream_t st,
+                    float speed = 0.f);
     int vits_decode_pass(gsv::VitsWorkspace& W, const int64_t* text_seq, int n_text, const int64_t* sem, int n_sem,
                          const float* ref_audio, int n_audio, const float* ge, const float* ge_adv,
                          const float* eps, uint64_t noise_seed, float noise_scale, float* audio, hipStream_t st,
-                         int* ovf, bool timed);
+                         int* ovf, bool timed, float speed = 0.f);
     // A segmented batch's front part in one pass (vits_front with fs): the utterances back to
     // back along the frame axis (the generator's layout) and along the text axis, zero gaps.
     struct FrontSeg {
@@ -388,7 +395,7 @@ struct gsv_engine {
     int vits_front(gsv::VitsWorkspace& W, const int64_t* text_seq, int n_text, const int64_t* sem, int n_sem,
                    const float* ref_audio, int n_audio, const float* ge, const float* ge_adv, const float* eps,
                    uint64_t noise_seed, float noise_scale, float* dcond_out, hipStream_t st,
-                   const FrontSeg* fs = nullptr);
+                   const FrontSeg* fs = nullptr, float speed = 0.f);
     int seg_front(hipStream_t st);
     int seg_front_tables(hipStream_t s);   // FrontSeg of vb_items into sgb (host build, one copy)            // the packed front of vb_items (vb_packed) into sgb.z / sgb.dcond
     // segmented vocoder batch (option "seg_vocoder", default 1): every utterance's front part

@@ -129,6 +129,9 @@ void noise_zp(const float* m, const float* logs, const float* eps, float scale, 
 void noise_zp_philox(const float* m, const float* logs, uint64_t seed, float scale, float* z, int n,
                      hipStream_t s);                                              // eps ~ Philox N(0,1)
 void flip_channels(const float* in, float* out, int C, int T, hipStream_t s);
+// x [C][T] -> out [C][T_out]: linear resample along time (align_corners = False, float32,
+// separately rounded multiplies and adds); the speech-rate control of the vocoder front
+void interp_linear(const float* x, int C, int T, int T_out, float* out, hipStream_t s);
 // Segmented-batch forms (utterances back to back along time, seg[t] = utterance or -1 in
 // a gap, off[i] its first column): the per-utterance inputs through device pointer tables;
 // gap columns are written as zeros.

@@ -564,6 +564,32 @@ void flip_channels(const float* in, float* out, int C, int T, hipStream_t s) {
     hipLaunchKernelGGL(k_flip, dim3((n + 255) / 256), dim3(256), 0, s, in, out, C, T);
 }
 
+// The speech-rate resample of the latent between enc_p.encoder2 and enc_p.proj (GPT-SoVITS
+// TextEncoder.forward: F.interpolate(y, size = T_out, mode = "linear")): x [C][T] ->
+// out [C][T_out], ATen's align_corners = False coordinates in float32.  Every multiply and add
+// is rounded on its own, so a numpy restatement with per-operation float32 rounding gives the
+// same bits: contraction is switched off for the body (hipcc contracts a * b + c into an fma by
+// default, and HIP's __fmul_rn / __fadd_rn are plain operators that it contracts all the same).
+// scale = (float)T / (float)T_out, computed by the host.
+__global__ void k_interp_linear(const float* x, int C, int T, int T_out, float scale, float* out) {
+#pragma clang fp contract(off)
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)C * T_out) return;
+    const int c = (int)(i / T_out), j = (int)(i - (long)c * T_out);
+    const float sj = scale * ((float)j + 0.5f);
+    const float src = fmaxf(sj - 0.5f, 0.f);
+    const int i0 = min((int)src, T - 1), i1 = i0 + (i0 < T - 1 ? 1 : 0);
+    const float l1 = src - (float)i0, l0 = 1.f - l1;
+    const float* xc = x + (long)c * T;
+    const float a = l0 * xc[i0], b = l1 * xc[i1];
+    out[i] = a + b;
+}
+void interp_linear(const float* x, int C, int T, int T_out, float* out, hipStream_t s) {
+    const long n = (long)C * T_out;
+    hipLaunchKernelGGL(k_interp_linear, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, C, T, T_out,
+                       (float)T / (float)T_out, out);
+}
+
 // ---- segmented-batch forms of the front's per-utterance kernels
 __global__ void k_cb_up2_seg(const int64_t* const* sems, const int* seg, const int* off, int T, const float* cb,
                              float* out) {

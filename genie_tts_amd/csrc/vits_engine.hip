@@ -439,10 +439,26 @@ static void run_ref_enc(VitsWorkspace& W, const RefEnc& R, const float* audio, i
     time_mean(W.r0, F, R.out_dim, ge, s);
 }
 
-// with_gen = false: the front part's buffers only (the packed front of a segmented batch)
-static int ensure_vits_ws(gsv_engine* e, VitsWorkspace& W, int T, int S, int n_audio, bool with_gen = true) {
+// gsv_vits_frames.  The float32 speed is widened to double before the division (a Python
+// double 1.1 and the float32 1.1 give different counts at n_sem = 11), so this is the one
+// place the count is computed.
+int gsv::vits_frames(int n_sem, float speed) {
+    if (n_sem < 0 || n_sem > (1 << 24)) return GSV_E_ARG;
+    const int T = 2 * n_sem;
+    if (speed == 0.0f || speed == 1.0f) return T;
+    if (!(speed >= 0.25f && speed <= 4.0f)) return GSV_E_ARG;   // NaN fails both comparisons
+    return (int)((double)T / (double)speed) + 1;
+}
+
+// with_gen = false: the front part's buffers only (the packed front of a segmented batch).
+// T_out (0: T): the frames after the speech-rate resample -- the front buffers hold
+// max(T, T_out) frames, the generator buffers T_out.
+static int ensure_vits_ws(gsv_engine* e, VitsWorkspace& W, int T, int S, int n_audio, bool with_gen = true,
+                          int T_out = 0) {
     const VitsWeights& V = e->vits;
-    const size_t gen = with_gen ? (size_t)V.upc * T * 20 : 0;   // max C*T over generator stages: upc/2^(i+1) * T*prod(u)
+    if (T_out <= 0) T_out = T;
+    const size_t gen = with_gen ? (size_t)V.upc * T_out * 20 : 0;   // max C*T over generator stages: upc/2^(i+1) * T*prod(u)
+    T = std::max(T, T_out);
     const int F = n_audio > 0 ? (n_audio + 1408 - 2048) / 640 + 1 : 0;
     if ((size_t)T <= W.cap_t && S <= W.cap_text && gen <= W.cap_gen && F <= W.cap_spec) return 0;
     // 1.25x headroom on every dimension that grows; the old buffers are retired (freed by
@@ -496,7 +512,7 @@ static int ensure_vits_ws(gsv_engine* e, VitsWorkspace& W, int T, int S, int n_a
 int gsv_engine::vits_decode(const int64_t* text_seq, int n_text, const int64_t* sem, int G,
                             const float* ref_audio, int n_audio, const float* ge_in,
                             const float* ge_adv_in, const float* eps, uint64_t noise_seed, float noise_scale,
-                            float* audio, hipStream_t s) {
+                            float* audio, hipStream_t s, float speed) {
     if (use_convh && !vovf) {   // stream-ordered zeroing: no null-stream call beside running lanes / captures
         if (hipMalloc(&vovf, 64) != hipSuccess || hipHostMalloc((void**)&vovf_host, 64, hipHostMallocDefault) != hipSuccess)
             return set_error(GSV_E_HIP, "overflow flag alloc");
@@ -508,12 +524,12 @@ int gsv_engine::vits_decode(const int64_t* text_seq, int n_text, const int64_t* 
         if (int r = vits_batch_finish(nullptr)) return r;
     if (!use_convh) {
         if (int r = vits_decode_pass(vws, text_seq, n_text, sem, G, ref_audio, n_audio, ge_in, ge_adv_in, eps,
-                                     noise_seed, noise_scale, audio, s, nullptr, timing))
+                                     noise_seed, noise_scale, audio, s, nullptr, timing, speed))
             return r;
         return vits_read_ms();
     }
     if (int r = vits_decode_pass(vws, text_seq, n_text, sem, G, ref_audio, n_audio, ge_in, ge_adv_in, eps, noise_seed,
-                                 noise_scale, audio, s, vovf, timing))
+                                 noise_scale, audio, s, vovf, timing, speed))
         return r;
     hipMemcpyAsync(vovf_host, vovf, 4, hipMemcpyDeviceToHost, s);
     if (hipStreamSynchronize(s) != hipSuccess) return set_error(GSV_E_HIP, "vits sync");
@@ -521,7 +537,7 @@ int gsv_engine::vits_decode(const int64_t* text_seq, int n_text, const int64_t* 
     hipMemsetAsync(vovf, 0, 4, s);
     ++vits_f32_reruns;
     if (int r = vits_decode_pass(vws, text_seq, n_text, sem, G, ref_audio, n_audio, ge_in, ge_adv_in, eps, noise_seed,
-                                 noise_scale, audio, s, nullptr, timing))
+                                 noise_scale, audio, s, nullptr, timing, speed))
         return r;
     return vits_read_ms();
 }
@@ -720,7 +736,7 @@ int gsv_engine::vits_launch_queued(hipStream_t s) {
     hipStreamWaitEvent(s, vev_in, 0);
     if (int r = vits_decode_pass(vws, u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge, u.ge_adv,
                                  u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0,
-                                 vcall_scale, u.audio, s, use_convh ? vovf : nullptr, timing))
+                                 vcall_scale, u.audio, s, use_convh ? vovf : nullptr, timing, u.speed))
         return r;
     if (use_convh) hipMemcpyAsync(vovf_host, vovf, 4, hipMemcpyDeviceToHost, s);
     hipEventRecord(vev_done, s);
@@ -743,7 +759,7 @@ int gsv_engine::vits_wait(hipStream_t caller) {
         if (int r = vits_decode_pass(vws, u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge,
                                      u.ge_adv, u.noise_mode == 1 ? u.eps : nullptr,
                                      u.noise_mode == 2 ? u.noise_seed : 0, vcall_scale, u.audio, vlast, nullptr,
-                                     timing))
+                                     timing, u.speed))
             return r;
         hipEventRecord(vev_done, vlast);
         if (hipEventSynchronize(vev_done) != hipSuccess) return set_error(GSV_E_HIP, "overlapped vocoder re-run");
@@ -927,22 +943,26 @@ static void vits_generator(const VitsWeights& V, float* const (&gb)[5], const fl
 
 // One utterance on stream s with workspace W.  ovf != NULL: the MRF convs run on
 // the f16-split path and OR 1 into *ovf on an fp16-range overflow.  noise: eps
-// (device [192, 2G]) if given, else Philox N(0,1) keyed by noise_seed when it is
-// non-zero, else zeros.  timed: phase events (ms[3]) around the pass.
+// (device [192, T']) if given, else Philox N(0,1) keyed by noise_seed when it is
+// non-zero, else zeros.  timed: phase events (ms[3]) around the pass.  speed: the speech
+// rate; T' = vits_frames(G, speed) frames from proj on (2G at speed 0 or 1).
 int gsv_engine::vits_decode_pass(VitsWorkspace& W, const int64_t* text_seq, int n_text, const int64_t* sem, int G,
                                  const float* ref_audio, int n_audio, const float* ge_in,
                                  const float* ge_adv_in, const float* eps, uint64_t noise_seed, float noise_scale,
-                                 float* audio, hipStream_t s, int* ovf, bool timed) {
+                                 float* audio, hipStream_t s, int* ovf, bool timed, float speed) {
     if (!vits.ready) return set_error(GSV_E_STATE, "VITS weights not loaded");
     if (G <= 0 || n_text <= 0) return set_error(GSV_E_ARG, "empty VITS input");
     if (2 * G > MHA_MAXK_HOST || n_text > MHA_MAXK_HOST) return set_error(GSV_E_CAPACITY, "sequence too long");
-    if (int r = ensure_vits_ws(this, W, 2 * G, n_text, version == GSV_V2PP ? 0 : n_audio)) return r;
+    const int Tp = vits_frames(G, speed);   // the frames after the resample: 2G at speed 1
+    if (Tp < 0) return set_error(GSV_E_ARG, "speed: 0.25 .. 4 (0 or 1: as recorded)");
+    if (Tp > VITS_MAXT_OUT) return set_error(GSV_E_CAPACITY, "resampled sequence too long");
+    if (int r = ensure_vits_ws(this, W, 2 * G, n_text, version == GSV_V2PP ? 0 : n_audio, true, Tp)) return r;
     SplitkScope sk(W.splitk, W.splitk_cap);
     ConvhScope cs(ovf, convh_tile, convt_f16, mrf_fused, convh_ws == 1 ? stream_cus(s) : 0);
     (void)hipGetLastError();   // the launches below are checked as one batch at the end
     if (timed) hipEventRecord(ev[4], s);
     if (int r = vits_front(W, text_seq, n_text, sem, G, ref_audio, n_audio, ge_in, ge_adv_in, eps, noise_seed,
-                           noise_scale, W.dcond, s))
+                           noise_scale, W.dcond, s, nullptr, speed))
         return r;
     float* const gb[5] = {W.g0, W.g1, W.g2, W.g3, W.g4};
     // the three resblocks of a stage on three streams (vits_fork, an unmasked engine stream)
@@ -962,7 +982,7 @@ int gsv_engine::vits_decode_pass(VitsWorkspace& W, const int64_t* text_seq, int 
             for (float*& p : W.gx) p = nullptr;   // (allocated ones stay in W.owned)
         }
     }
-    vits_generator(vits, gb, W.z, 2 * G, W.dcond, 0, nullptr, audio, s, sd, sd ? W.gx : nullptr);
+    vits_generator(vits, gb, W.z, Tp, W.dcond, 0, nullptr, audio, s, sd, sd ? W.gx : nullptr);
     if (timed) hipEventRecord(ev[5], s);   // read by vits_read_ms once the pass is known to be final
     return hipGetLastError() == hipSuccess ? 0 : set_error(GSV_E_HIP, "vits launch");
 }
@@ -979,15 +999,15 @@ int gsv_engine::vits_decode_pass(VitsWorkspace& W, const int64_t* text_seq, int 
 int gsv_engine::vits_front(VitsWorkspace& W, const int64_t* text_seq, int n_text, const int64_t* sem, int G,
                            const float* ref_audio, int n_audio, const float* ge_in, const float* ge_adv_in,
                            const float* eps, uint64_t noise_seed, float noise_scale, float* dcond_out,
-                           hipStream_t s, const FrontSeg* fs) {
+                           hipStream_t s, const FrontSeg* fs, float speed) {
     const VitsWeights& V = vits;
     if (!V.ready) return set_error(GSV_E_STATE, "VITS weights not loaded");
     const bool pp = version == GSV_V2PP;
     const int* sT = fs ? fs->segT : nullptr;
     const int* sS = fs ? fs->segS : nullptr;
-    int T, S;
-    if (fs) {
-        T = fs->Tt;
+    int T, S, To;   // To: the frames after the speech-rate resample (T unless 0 != speed != 1)
+    if (fs) {       // the packed front carries no resample: a batch with one declines to pack
+        To = T = fs->Tt;
         S = fs->St;
         if (int r = ensure_vits_ws(this, W, T, S, 0, false)) return r;
     } else {
@@ -997,7 +1017,10 @@ int gsv_engine::vits_front(VitsWorkspace& W, const int64_t* text_seq, int n_text
         T = 2 * G;
         S = n_text;
         if (T > MHA_MAXK_HOST || S > MHA_MAXK_HOST) return set_error(GSV_E_CAPACITY, "sequence too long");
-        if (int r = ensure_vits_ws(this, W, T, S, pp ? 0 : n_audio)) return r;
+        To = vits_frames(G, speed);
+        if (To < 0) return set_error(GSV_E_ARG, "speed: 0.25 .. 4 (0 or 1: as recorded)");
+        if (To > VITS_MAXT_OUT) return set_error(GSV_E_CAPACITY, "resampled sequence too long");
+        if (int r = ensure_vits_ws(this, W, T, S, pp ? 0 : n_audio, true, To)) return r;
     }
     // ---- conditioning: ge (flow cond / dec.cond) and MRTE vector
     const float* ge;
@@ -1060,7 +1083,16 @@ int gsv_engine::vits_front(VitsWorkspace& W, const int64_t* text_seq, int n_text
     conv1d(co, s);
     conv1d(cargs(V.c_post, W.a, T, W.y, CV_STORE, sT), s);
     attn_encoder(this, V.enc2, W.y, T, W.qkv, W.att, W.a, W.ffn, s, sT, fs ? fs->rowT : nullptr);
-    conv1d(cargs(V.proj, W.y, T, W.stats, CV_STORE, sT), s);
+    // ---- speech rate: y resampled to To frames (TextEncoder.forward's F.interpolate between
+    // encoder2 and proj); no attention runs past this point, W.att is free after encoder2.
+    // Everything below runs at To frames.
+    const float* yp = W.y;
+    if (To != T) {
+        interp_linear(W.y, 192, T, To, W.att, s);
+        yp = W.att;
+        T = To;
+    }
+    conv1d(cargs(V.proj, yp, T, W.stats, CV_STORE, sT), s);
     // ---- z_p = m_p + eps*exp(logs_p)*noise_scale
     if (fs)
         noise_zp_philox_seg(W.stats, W.stats + (size_t)192 * T, fs->seeds, sT, fs->offT, fs->lenT, noise_scale, W.z,
@@ -1126,7 +1158,7 @@ int gsv_engine::vits_decode_batch(int n, const gsv_vits_item* it, float noise_sc
         const gsv_vits_item& u = it[0];
         return vits_decode(u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge, u.ge_adv,
                            u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0, noise_scale,
-                           u.audio, s);
+                           u.audio, s, u.speed);
     }
     vb_items.assign(it, it + n);
     if (int r = vits_batch_launch(noise_scale, s, true)) return r;
@@ -1361,7 +1393,9 @@ int gsv_engine::vits_batch_launch(float noise_scale, hipStream_t s, bool join) {
         for (int i = 0; i < n; ++i) {
             if (vb_items[i].n_sem <= 0) return set_error(GSV_E_ARG, "empty VITS input");
             sgb.h_off[i] = T;
-            sgb.h_len[i] = 2 * vb_items[i].n_sem;
+            sgb.h_len[i] = vits_frames(vb_items[i].n_sem, vb_items[i].speed);   // laid out by the resampled frames
+            if (sgb.h_len[i] < 0) return set_error(GSV_E_ARG, "speed: 0.25 .. 4 (0 or 1: as recorded)");
+            if (sgb.h_len[i] > VITS_MAXT_OUT) return set_error(GSV_E_CAPACITY, "resampled sequence too long");
             T += sgb.h_len[i] + (i + 1 < n ? SEG_GAP : 0);
         }
         if (int r = seg_reserve(n, T)) return r;
@@ -1377,13 +1411,15 @@ int gsv_engine::vits_batch_launch(float noise_scale, hipStream_t s, bool join) {
             seg_fill(sgb.seg[i], f * T, sgb.off, sgb.len, n, (int)f, s);
             if (i < 5) f *= V.up_rate[i];
         }
-        // the front part packed too when every item carries its conditioning vectors and
-        // draws no explicit eps (else: each item's front on a lane)
+        // the front part packed too when every item carries its conditioning vectors, draws
+        // no explicit eps and keeps its frame count (no speech-rate resample: the packed tables
+        // describe one frame layout); else: each item's front on a lane
         bool packed = seg_front_on;
         const bool pp = version == GSV_V2PP;
         for (int i = 0; i < n && packed; ++i) {
             const gsv_vits_item& u = vb_items[i];
             packed = u.noise_mode != 1 && u.n_text > 0 && 2 * u.n_sem <= MHA_MAXK_HOST &&
+                     sgb.h_len[i] == 2 * u.n_sem &&
                      u.n_text <= MHA_MAXK_HOST && u.ge != nullptr && (!pp || u.ge_adv != nullptr);
         }
         if (packed) {
@@ -1398,15 +1434,16 @@ int gsv_engine::vits_batch_launch(float noise_scale, hipStream_t s, bool join) {
     // allocates (a hipMalloc beside another thread's stream capture or launches is avoided).
     for (int l = 0; l < K; ++l) {
         if (seg && vb_packed) break;   // the packed front: one workspace, sized below
-        int T = 0, S = 0, A = 0;
+        int T = 0, S = 0, A = 0, To = 0;
         for (int i = l; i < n; i += K) {
             T = std::max(T, 2 * vb_items[i].n_sem);
+            To = std::max(To, vits_frames(vb_items[i].n_sem, vb_items[i].speed));   // (< 0: the lane reports it)
             S = std::max(S, vb_items[i].n_text);
             A = std::max(A, version == GSV_V2PP ? 0 : vb_items[i].n_audio);
         }
-        if (T > MHA_MAXK_HOST || S > MHA_MAXK_HOST) continue;   // the lane reports the capacity error
+        if (T > MHA_MAXK_HOST || S > MHA_MAXK_HOST || To > VITS_MAXT_OUT) continue;   // the lane reports the capacity error
         // with the generator buffers, as the lanes' own ensure_vits_ws calls ask (vits_front, the pass)
-        if (int r = ensure_vits_ws(this, vlanes[l].ws, std::max(T, 2), std::max(S, 2), A)) return r;
+        if (int r = ensure_vits_ws(this, vlanes[l].ws, std::max(T, 2), std::max(S, 2), A, true, std::max(To, 2))) return r;
     }
     if (seg && vb_packed)
         if (int r = ensure_vits_ws(this, sgb.fw, sgb.T, sgb.St, 0, false)) return r;
@@ -1435,12 +1472,13 @@ int gsv_engine::vits_batch_launch(float noise_scale, hipStream_t s, bool join) {
                 break;
             } else if (seg) {   // the front part; z and dec.cond(ge) into the batch buffers
                 VitsWorkspace& W = L.ws;
-                r = ensure_vits_ws(this, W, 2 * u.n_sem, u.n_text, version == GSV_V2PP ? 0 : u.n_audio);
+                r = ensure_vits_ws(this, W, 2 * u.n_sem, u.n_text, version == GSV_V2PP ? 0 : u.n_audio, true,
+                                   sgb.h_len[i]);
                 if (!r) {
                     SplitkScope sk(W.splitk, W.splitk_cap);
                     r = vits_front(W, u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge, u.ge_adv,
                                    u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0,
-                                   vb_scale, sgb.dcond + (size_t)i * vits.upc, L.st);
+                                   vb_scale, sgb.dcond + (size_t)i * vits.upc, L.st, nullptr, u.speed);
                 }
                 if (!r)
                     hipMemcpy2DAsync(sgb.z + sgb.h_off[i], (size_t)sgb.T * 4, W.z, (size_t)sgb.h_len[i] * 4,
@@ -1449,7 +1487,7 @@ int gsv_engine::vits_batch_launch(float noise_scale, hipStream_t s, bool join) {
                 r = vits_decode_pass(L.ws, u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge,
                                      u.ge_adv, u.noise_mode == 1 ? u.eps : nullptr,
                                      u.noise_mode == 2 ? u.noise_seed : 0, vb_scale, u.audio, L.st,
-                                     use_convh ? vflags + i : nullptr, false);
+                                     use_convh ? vflags + i : nullptr, false, u.speed);
             }
             if (r) {
                 vb_rcs[l] = r;
@@ -1550,7 +1588,7 @@ int gsv_engine::vits_batch_finish(hipStream_t s) {
             if (int r = vits_decode_pass(vws, u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge,
                                          u.ge_adv, u.noise_mode == 1 ? u.eps : nullptr,
                                          u.noise_mode == 2 ? u.noise_seed : 0, vb_scale, u.audio, s, nullptr,
-                                         false))
+                                         false, u.speed))
                 return r;
         }
     }
@@ -1612,6 +1650,26 @@ extern "C" int gsv_vits_decode(gsv_engine* eng, const int64_t* text_seq, int32_t
                             noise_scale, audio, sc.st());
 }
 
+// An item the vocoder entries accept: its noise source, output buffer and speech rate.
+static bool vits_item_ok(const gsv_vits_item& u) {
+    return u.noise_mode >= 0 && u.noise_mode <= 2 && (u.noise_mode != 1 || u.eps) && u.audio &&
+           vits_frames(1, u.speed) > 0;
+}
+
+extern "C" int gsv_vits_frames(int32_t n_sem, float speed) { return vits_frames(n_sem, speed); }
+
+extern "C" int gsv_vits_decode_item(gsv_engine* eng, const gsv_vits_item* item, float noise_scale, void* stream) {
+    if (!eng) return set_error(GSV_E_ARG, "null engine");
+    if (!item || !vits_item_ok(*item)) return set_error(GSV_E_ARG, "bad vocoder item");
+    hipSetDevice(eng->device);
+    if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
+    StreamScope sc(eng, stream);
+    const gsv_vits_item& u = *item;
+    return eng->vits_decode(u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge, u.ge_adv,
+                            u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0, noise_scale,
+                            u.audio, sc.st(), u.speed);
+}
+
 extern "C" int gsv_vits_decode_batch(gsv_engine* eng, int32_t n, const gsv_vits_item* items, float noise_scale,
                                      void* stream) {
     if (!eng) return set_error(GSV_E_ARG, "null engine");
@@ -1619,8 +1677,7 @@ extern "C" int gsv_vits_decode_batch(gsv_engine* eng, int32_t n, const gsv_vits_
     hipSetDevice(eng->device);
     if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
     for (int i = 0; i < n; ++i)
-        if (items[i].noise_mode < 0 || items[i].noise_mode > 2 || (items[i].noise_mode == 1 && !items[i].eps) ||
-            !items[i].audio)
+        if (!vits_item_ok(items[i]))
             return set_error(GSV_E_ARG, "bad vocoder item " + std::to_string(i));
     StreamScope sc(eng, stream);
     return eng->vits_decode_batch(n, items, noise_scale, sc.st());
@@ -1628,8 +1685,7 @@ extern "C" int gsv_vits_decode_batch(gsv_engine* eng, int32_t n, const gsv_vits_
 
 extern "C" int gsv_vits_decode_async(gsv_engine* eng, const gsv_vits_item* item, float noise_scale, void* stream) {
     if (!eng) return set_error(GSV_E_ARG, "null engine");
-    if (!item || item->noise_mode < 0 || item->noise_mode > 2 || (item->noise_mode == 1 && !item->eps) || !item->audio)
-        return set_error(GSV_E_ARG, "bad vocoder item");
+    if (!item || !vits_item_ok(*item)) return set_error(GSV_E_ARG, "bad vocoder item");
     hipSetDevice(eng->device);
     if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
     return eng->vits_async(*item, noise_scale, (hipStream_t)stream);
@@ -1648,8 +1704,7 @@ extern "C" int gsv_vits_decode_batch_async(gsv_engine* eng, int32_t n, const gsv
     hipSetDevice(eng->device);
     if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
     for (int i = 0; i < n; ++i)
-        if (items[i].noise_mode < 0 || items[i].noise_mode > 2 || (items[i].noise_mode == 1 && !items[i].eps) ||
-            !items[i].audio)
+        if (!vits_item_ok(items[i]))
             return set_error(GSV_E_ARG, "bad vocoder item " + std::to_string(i));
     if (int r = eng->vits_batch_finish(nullptr)) return r;
     if (int r = eng->vits_wait(nullptr)) return r;
@@ -1713,6 +1768,12 @@ extern "C" int gsv_debug_conv1d(const float* x, int cin, int tin, const float* w
     a.part = splitk_ws; a.part_cap = splitk_cap;
     conv1d(a, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? 0 : set_error(GSV_E_HIP, "debug conv");
+}
+
+extern "C" int gsv_debug_interp_linear(const float* x, int c, int t, int t_out, float* out, void* stream) {
+    if (!x || !out || c <= 0 || t <= 0 || t_out <= 0) return set_error(GSV_E_ARG, "bad args");
+    interp_linear(x, c, t, t_out, out, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? 0 : set_error(GSV_E_HIP, "debug interp");
 }
 
 extern "C" int gsv_debug_conv1d_h(const float* x, int cin, int tin, const void* wh, const float* scale,

@@ -79,6 +79,7 @@ class VitsItem(ctypes.Structure):
         ("ge", ctypes.c_void_p), ("ge_adv", ctypes.c_void_p),
         ("eps", ctypes.c_void_p), ("noise_seed", ctypes.c_uint64), ("noise_mode", ctypes.c_int32),
         ("audio", ctypes.c_void_p),
+        ("speed", ctypes.c_float),
     ]
 
 
@@ -131,6 +132,9 @@ def lib():
         L.gsv_vits_decode_batch.argtypes = [vp, i32, ctypes.POINTER(VitsItem), ctypes.c_float, vp]
         L.gsv_vits_decode_async.argtypes = [vp, ctypes.POINTER(VitsItem), ctypes.c_float, vp]
         L.gsv_vits_wait.argtypes = [vp, vp]
+        L.gsv_vits_frames.argtypes = [i32, ctypes.c_float]
+        L.gsv_vits_decode_item.argtypes = [vp, ctypes.POINTER(VitsItem), ctypes.c_float, vp]
+        L.gsv_debug_interp_linear.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
         L.gsv_vits_decode_batch_async.argtypes = [vp, i32, ctypes.POINTER(VitsItem), ctypes.c_float, vp]
         L.gsv_vits_batch_wait.argtypes = [vp, vp]
         L.gsv_t2s_prefetch.argtypes = [vp, ctypes.POINTER(Utt), ctypes.POINTER(Sampler), vp]
@@ -179,7 +183,8 @@ EXPORTED = (
     "gsv_vits_decode_async",
     "gsv_vits_wait", "gsv_t2s_prefetch", "gsv_t2s_generate_start", "gsv_t2s_generate_finish",
     "gsv_vits_decode_batch_async", "gsv_vits_batch_wait", "gsv_ref_encode", "gsv_roberta_batch",
-    "gsv_f16_exact", "gsv_request_stop", "gsv_debug_hbm_copy",
+    "gsv_f16_exact", "gsv_request_stop", "gsv_debug_hbm_copy", "gsv_vits_frames", "gsv_vits_decode_item",
+    "gsv_debug_interp_linear",
 )
 
 
@@ -207,6 +212,20 @@ def f16_exact(values) -> int:
     if rc < 0:
         _check(rc, "gsv_f16_exact")
     return int(bad.value)
+
+
+def vits_frames(n_sem: int, speed: float = 1.0) -> int:
+    """Frames T' the vocoder runs at for n_sem semantic tokens at speech rate `speed`
+    (gsv_vits_frames, the one place the count is computed; the audio is 640 T' samples).
+    ValueError for a speed outside [0.25, 4] or not finite; 0 and 1 mean no resample."""
+    try:
+        sp = float(speed)
+    except (TypeError, ValueError):
+        raise ValueError(f"speed must be a number, not {speed!r}") from None
+    n = lib().gsv_vits_frames(int(n_sem), ctypes.c_float(sp))
+    if n < 0:
+        raise ValueError(f"speed must be finite and within 0.25 .. 4.0, not {speed!r}")
+    return n
 
 
 def _check(rc: int, what: str):
@@ -477,13 +496,21 @@ class Engine:
         return self._dev(np.asarray(x).reshape(-1) if not isinstance(x, t.Tensor) else x.reshape(-1), t.int64)
 
     def vits_decode(self, text_seq, pred_semantic, ref_audio=None, ge=None, ge_advanced=None,
-                    eps=None, noise_scale: float = 0.5, noise_seed: Optional[int] = None):
-        """vits_fp32.onnx for one utterance.  Noise of z_p: eps (tensor/array [192, 2G]) if
-        given, else the engine's Philox N(0,1) stream keyed by noise_seed if given, else zeros."""
+                    eps=None, noise_scale: float = 0.5, noise_seed: Optional[int] = None, speed: float = 1.0):
+        """vits_fp32.onnx for one utterance.  Noise of z_p: eps (tensor/array [192, T']) if
+        given, else the engine's Philox N(0,1) stream keyed by noise_seed if given, else zeros.
+        speed: the speech rate (0.25 .. 4; T' = vits_frames(G, speed) frames, 640 T' samples)."""
         if noise_seed is not None and eps is None:
             return self.vits_decode_batch([dict(text_seq=text_seq, pred_semantic=pred_semantic, ref_audio=ref_audio,
-                                                ge=ge, ge_advanced=ge_advanced, noise_seed=noise_seed)],
-                                          noise_scale)[0]
+                                                ge=ge, ge_advanced=ge_advanced, noise_seed=noise_seed,
+                                                speed=speed)], noise_scale)[0]
+        if float(speed) != 1.0:
+            item, keep, audio = self._vits_item(dict(text_seq=text_seq, pred_semantic=pred_semantic,
+                                                     ref_audio=ref_audio, ge=ge, ge_advanced=ge_advanced, eps=eps,
+                                                     speed=speed))
+            _check(lib().gsv_vits_decode_item(self.h, ctypes.byref(item), ctypes.c_float(noise_scale), _stream()),
+                   "gsv_vits_decode_item")
+            return audio
         t = self.torch
         ts = self._ids(text_seq)
         sem = self._ids(pred_semantic)
@@ -510,21 +537,29 @@ class Engine:
         g = None if g is None else self._dev(g, t.float32).reshape(-1)
         ga = it.get("ge_advanced")
         ga = None if ga is None else self._dev(ga, t.float32).reshape(-1)
+        speed = it.get("speed")
+        speed = 1.0 if speed is None else float(speed)
+        frames = vits_frames(G, speed)
         e = it.get("eps")
-        e = None if e is None else self._dev(e, t.float32).reshape(192, 2 * G)
+        e = None if e is None else self._dev(e, t.float32).reshape(192, frames)
         seed = it.get("noise_seed")
         mode = 1 if e is not None else (2 if seed is not None else 0)
-        audio = t.empty((1280 * G,), dtype=t.float32, device=self.dev)
+        audio = t.empty((640 * frames,), dtype=t.float32, device=self.dev)
         item = VitsItem(ts.data_ptr(), ts.numel(), sem.data_ptr(), G, 0 if ra is None else ra.data_ptr(),
                         0 if ra is None else ra.numel(), 0 if g is None else g.data_ptr(),
                         0 if ga is None else ga.data_ptr(), 0 if e is None else e.data_ptr(),
-                        int(seed or 0) & 0xFFFFFFFFFFFFFFFF, mode, audio.data_ptr())
+                        int(seed or 0) & 0xFFFFFFFFFFFFFFFF, mode, audio.data_ptr(), speed)
         return item, [ts, sem, ra, g, ga, e], audio
+
+    @staticmethod
+    def vits_frames(n_sem: int, speed: float = 1.0) -> int:
+        """Frames of the vocoder at this speech rate (module-level vits_frames)."""
+        return vits_frames(n_sem, speed)
 
     def vits_decode_batch(self, items: Sequence[dict], noise_scale: float = 0.5):
         """Several vocoder calls at once (concurrent engine lanes).  Each item: text_seq,
         pred_semantic, and ref_audio (V2) or ge + ge_advanced (V2ProPlus); optional eps or
-        noise_seed.  Returns one audio tensor [1280 G] per item."""
+        noise_seed, optional speed.  Returns one audio tensor [640 T'] per item (1280 G at speed 1)."""
         arr = (VitsItem * len(items))()
         keep, outs = [], []
         for i, it in enumerate(items):
@@ -568,7 +603,7 @@ class Engine:
 
     def vits_decode_async(self, item: dict, noise_scale: float = 0.5):
         """Start one vocoder call on the vocoder CUs (gsv_vits_decode_async) and return its
-        audio tensor [1280 G], valid after vits_wait().  item as for vits_decode_batch."""
+        audio tensor [640 T'], valid after vits_wait().  item as for vits_decode_batch."""
         it, keep, audio = self._vits_item(item)
         _check(lib().gsv_vits_decode_async(self.h, ctypes.byref(it), ctypes.c_float(noise_scale), _stream()),
                "gsv_vits_decode_async")

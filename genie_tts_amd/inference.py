@@ -2,7 +2,8 @@
 
 `GENIE.tts` has the reference's signature (Inference.py:16-61): it takes the
 reference-audio features and the five sessions of a `GSVModel`, runs T2S, the
-EOS filter and the vocoder, and returns `audio f32 [1280*G]`.  When the
+EOS filter and the vocoder, and returns `audio f32 [1280*G]` (`[640*T']` at a
+speech rate `speed` other than 1, T' = Engine.vits_frames(G, speed)).  When the
 sessions are this package's engine-backed ones (always, through
 `model_manager`), T2S is one `gsv_t2s_generate` call: encoder, prefill, the
 whole decode loop as one persistent kernel launch (per-step hipGraphs only as
@@ -24,7 +25,7 @@ from typing import Callable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from .engine import EngineStopped, Sampler, request_stop_all
+from .engine import EngineStopped, Sampler, request_stop_all, vits_frames
 from .sessions import (EncoderSession, FirstStageDecoderSession, StageDecoderSession, VitsSession,
                        PromptEncoderSession)
 
@@ -101,7 +102,10 @@ class GENIE:
     def tts(self, text: Union[str, np.ndarray], prompt_audio: ReferenceAudio, encoder, first_stage_decoder,
             stage_decoder, vocoder, prompt_encoder=None, language: str = "japanese",
             text_bert: Optional[np.ndarray] = None, g2p: Optional[Callable] = None,
-            sampler: Optional[Sampler] = None) -> Optional[np.ndarray]:
+            sampler: Optional[Sampler] = None, speed: float = 1.0) -> Optional[np.ndarray]:
+        """speed: the speech rate (0.25 .. 4, GPT-SoVITS's `speed`; 1: the reference's audio)."""
+        vits_frames(0, speed)          # ValueError for a bad rate, before any GPU work
+        rate = {} if float(speed) == 1.0 else {"speed": float(speed)}
         if isinstance(text, str):
             if g2p is None:
                 raise ValueError("text input needs a g2p(text, language) callable (G2P is outside this engine)")
@@ -124,15 +128,15 @@ class GENIE:
             sem = eos_filter(sem)
         if prompt_encoder is None:
             return vocoder.run(None, {"text_seq": text_seq, "pred_semantic": sem,
-                                      "ref_audio": prompt_audio.audio_32k})[0]
+                                      "ref_audio": prompt_audio.audio_32k, **rate})[0]
         prompt_audio.update_global_emb(prompt_encoder)
         return vocoder.run(None, {"text_seq": text_seq, "pred_semantic": sem, "ge": prompt_audio.global_emb,
-                                  "ge_advanced": prompt_audio.global_emb_advanced})[0]
+                                  "ge_advanced": prompt_audio.global_emb_advanced, **rate})[0]
 
     def tts_stream(self, texts: Sequence[Union[str, np.ndarray]], prompt_audio: ReferenceAudio, encoder,
                    first_stage_decoder, stage_decoder, vocoder, prompt_encoder=None, language: str = "japanese",
                    text_bert: Optional[np.ndarray] = None, g2p: Optional[Callable] = None,
-                   sampler: Optional[Sampler] = None, vocoder_cus: int = 64):
+                   sampler: Optional[Sampler] = None, vocoder_cus: int = 64, speed: float = 1.0):
         """tts over a list of sentences, yielding each sentence's audio in order (the
         reference runs them one after the other: TTSPlayer._tts_worker_loop,
         Core/TTSPlayer.py:56-107).  Engine-backed sessions pipeline them: sentence i's
@@ -140,14 +144,15 @@ class GENIE:
         the rest (gsv_vits_decode_async), and sentence i+1's encoder + prefill run on
         those CUs during sentence i's decode (gsv_t2s_prefetch), so sentence i is
         yielded once sentence i+1's T2S is done.  Same tokens and audio as calling
-        tts per sentence."""
+        tts per sentence.  speed: the speech rate of every sentence."""
+        vits_frames(0, speed)          # a bad rate fails here, before anything is started
         eng = _engine_of(encoder, first_stage_decoder, stage_decoder, vocoder)
         if eng is None or vocoder_cus <= 0 or len(texts) < 2:
             for t in texts:
                 if self.stop_event.is_set():
                     return
                 yield self.tts(t, prompt_audio, encoder, first_stage_decoder, stage_decoder, vocoder, prompt_encoder,
-                               language, text_bert, g2p, sampler)
+                               language, text_bert, g2p, sampler, speed)
             return
         prev_cus = eng.vocoder_cus     # restored when the stream ends: later single-sentence and
         if prev_cus != vocoder_cus:    # batched calls keep every CU (decode groups, lanes)
@@ -198,8 +203,8 @@ class GENIE:
                     done, pending = pending, None
                     yield done.cpu().numpy()
                 G = sem.size
-                eps = vocoder.eps_fn(G) if vocoder.eps_fn else None
-                item = dict(text_seq=text_seq, pred_semantic=sem, **cond)
+                eps = vocoder.eps(G, speed)
+                item = dict(text_seq=text_seq, pred_semantic=sem, speed=speed, **cond)
                 if eps is not None:
                     item["eps"] = eps
                 else:
@@ -251,14 +256,16 @@ class GENIE:
         y[0, -1] = 0
         return np.expand_dims(y[:, -idx:], axis=0)
 
-    def tts_batch(self, items: Sequence[tuple], prompt_audio: ReferenceAudio, model, sampler: Sampler) -> List[np.ndarray]:
+    def tts_batch(self, items: Sequence[tuple], prompt_audio: ReferenceAudio, model, sampler: Sampler,
+                  speed: Union[float, Sequence[float]] = 1.0) -> List[np.ndarray]:
         """Batched synthesis for one character and reference: items are
         (text_seq, text_bert|None[, force_steps]).  All sequences decode together
         (one multi-sequence persistent launch, ragged: a finished sequence drops out);
         the vocoder runs each utterance's text/flow part on concurrent lanes and the
-        generator once over the whole batch (gsv_vits_decode_batch)."""
+        generator once over the whole batch (gsv_vits_decode_batch).  speed: one speech rate
+        for all items, or one per item."""
         toks = self.tts_batch_t2s(items, prompt_audio, model, sampler)
-        wavs = self.tts_batch_vocoder(items, toks, prompt_audio, model)
+        wavs = self.tts_batch_vocoder(items, toks, prompt_audio, model, speed=speed)
         return [w if isinstance(w, np.ndarray) else w.cpu().numpy() for w in wavs]
 
     def tts_batch_t2s(self, items: Sequence[tuple], prompt_audio: ReferenceAudio, model, sampler: Sampler):
@@ -272,12 +279,17 @@ class GENIE:
         return model.ENGINE.t2s_generate(utts, sampler)
 
     def tts_batch_vocoder(self, items: Sequence[tuple], toks, prompt_audio: ReferenceAudio, model,
-                          overlapped: bool = False):
+                          overlapped: bool = False, speed: Union[float, Sequence[float]] = 1.0):
         """The vocoder half of tts_batch.  overlapped=True (engine-backed vocoder only) starts
         the batch on the vocoder lanes and returns device tensors that are valid after
         model.ENGINE.vits_batch_wait(); the T2S of the next batch runs beside it
         (gsv_vits_decode_batch_async)."""
         eng = model.ENGINE
+        speeds = [float(speed)] * len(items) if np.ndim(speed) == 0 else [float(v) for v in speed]
+        if len(speeds) != len(items):
+            raise ValueError("speed: one value, or one per item")
+        for v in speeds:
+            vits_frames(0, v)          # ValueError for a bad rate, before any GPU work
         if model.PROMPT_ENCODER is not None:
             prompt_audio.update_global_emb(model.PROMPT_ENCODER)
         cond = ({"ref_audio": prompt_audio.audio_32k} if model.PROMPT_ENCODER is None else
@@ -285,11 +297,12 @@ class GENIE:
         if model.PROMPT_ENCODER is None and getattr(model.VITS, "engine", None) is eng:
             cond = model.VITS.v2_cond(prompt_audio.audio_32k)   # the reference branch once per reference
         if getattr(model.VITS, "engine", None) is not eng:
-            return [model.VITS.run(None, {"text_seq": it[0], "pred_semantic": tok.reshape(1, 1, -1), **cond})[0]
-                    for it, tok in zip(items, toks)]
+            return [model.VITS.run(None, {"text_seq": it[0], "pred_semantic": tok.reshape(1, 1, -1), **cond,
+                                          **({} if v == 1.0 else {"speed": v})})[0]
+                    for it, tok, v in zip(items, toks, speeds)]
         # engine-backed vocoder: all utterances on concurrent lanes (gsv_vits_decode_batch)
-        batch = [dict(text_seq=it[0], pred_semantic=tok, noise_seed=model.VITS.next_seed(), **cond)
-                 for it, tok in zip(items, toks)]
+        batch = [dict(text_seq=it[0], pred_semantic=tok, noise_seed=model.VITS.next_seed(), speed=v, **cond)
+                 for it, tok, v in zip(items, toks, speeds)]
         if overlapped:
             return eng.vits_decode_batch_async(batch, model.VITS.noise_scale)
         return eng.vits_decode_batch(batch, model.VITS.noise_scale)

@@ -58,7 +58,7 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
     import numpy as np
     import genie_tts_amd as genie
     from genie_tts_amd import api, audio as A
-    from genie_tts_amd.engine import make_sampler
+    from genie_tts_amd.engine import make_sampler, vits_frames
     from genie_tts_amd.inference import tts_client
     from genie_tts_amd.model_manager import model_manager
     from genie_tts_amd.text_splitter import TextSplitter
@@ -112,9 +112,16 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
         if not sents:
             reply(kind="end", id=msg["id"])
             return
+        speed = msg.get("speed")
+        try:                          # a bad rate ends this request only (HTTP 400), never a round
+            speed = 1.0 if speed is None else float(speed)
+            vits_frames(0, speed)
+        except (TypeError, ValueError) as e:
+            reply(kind="error", id=msg["id"], detail=f"speed: {e}")
+            return
         pending.append({"id": msg["id"], "character_name": msg["character_name"], "sentences": sents, "next": 0,
                         "force_steps": int(msg.get("force_steps") or 0), "save_path": msg.get("save_path"),
-                        "chunks": []})
+                        "chunks": [], "speed": speed})
 
     inflight: List[tuple] = []      # [(group, sentence indexes, wavs, engine)] of the overlapped vocoder
 
@@ -178,7 +185,9 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
             finish_inflight()
             eng = m.ENGINE if getattr(m.VITS, "engine", None) is m.ENGINE else None
             overlapped = pipeline and eng is not None
-            wavs = tts_client.tts_batch_vocoder(items, toks, ref, m, overlapped=overlapped)
+            speeds = [r["speed"] for r in group]
+            rate = {} if all(v == 1.0 for v in speeds) else {"speed": speeds}
+            wavs = tts_client.tts_batch_vocoder(items, toks, ref, m, overlapped=overlapped, **rate)
         except Exception as e:       # noqa: BLE001
             finish_inflight()
             for r in group:
@@ -377,7 +386,7 @@ class Router:
 def create_app(router: Router):
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import StreamingResponse
-    from pydantic import BaseModel
+    from pydantic import BaseModel, Field
 
     from .api import SUPPORTED_AUDIO_EXTS, _norm_language
 
@@ -411,6 +420,8 @@ def create_app(router: Router):
         split_sentence: bool = False
         save_path: Optional[str] = None
         force_steps: int = 0          # benchmark knob (random weights never emit EOS); 0 = the reference's rule
+        # speech rate (GPT-SoVITS's `speed`): sentence i is 640 * gsv_vits_frames(G_i, speed) samples
+        speed: float = Field(1.0, ge=0.25, le=4.0)
 
     def check(res: List[dict]) -> None:
         bad = [r for r in res if r["kind"] == "error"]
@@ -443,13 +454,13 @@ def create_app(router: Router):
     async def tts_endpoint(payload: TTSPayload):
         gen = router.tts(character_name=payload.character_name, text=payload.text,
                          split_sentence=payload.split_sentence, save_path=payload.save_path,
-                         force_steps=payload.force_steps)
+                         force_steps=payload.force_steps, speed=payload.speed)
         try:    # surface "not found" as 404 before the stream starts, as the reference does
             first = await gen.__anext__()
         except StopAsyncIteration:
             first = None
         except RuntimeError as e:
-            code = 404 if "not found" in str(e) else 500
+            code = 404 if "not found" in str(e) else 400 if str(e).startswith("speed:") else 500
             raise HTTPException(status_code=code, detail=str(e))
 
         async def body():

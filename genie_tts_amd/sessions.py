@@ -172,7 +172,12 @@ class VitsSession(_Session):
     z_p noise: the graph draws RandomNormalLike x noise_scale (0.5) on every call
     (vits(v2)#6490).  noise="philox" (default) draws it from the engine's device
     Philox N(0,1) stream, a fresh seed per call; noise="zero" is the deterministic
-    test mode; `eps_fn(G) -> [192, 2G]` fixes it explicitly."""
+    test mode; `eps_fn(G) -> [192, 2G]` fixes it explicitly.
+
+    Speech rate: an optional "speed" feed entry (a scalar, 0.25 .. 4, default 1; the graph was
+    exported with it fixed at 1) resamples the latent to T' = engine.vits_frames(G, speed) frames
+    before enc_p.proj, so the audio is 640 T' samples at unchanged pitch.  eps_fn is then called
+    as `eps_fn(G, T') -> [192, T']`."""
     OUTPUTS = (NodeArg("audio", ("1280*G",), "tensor(float)"),)
 
     def __init__(self, engine, version: str, noise_scale: float = 0.5, eps_fn=None, noise: str = "philox",
@@ -208,6 +213,13 @@ class VitsSession(_Session):
             self._ref, self._ref_key = ref_audio, key
         return dict(ge=self._ref_ge)
 
+    def eps(self, G: int, speed: float = 1.0):
+        """The explicit noise of one call (None without eps_fn): [192, 2G], or [192, T'] at a speed."""
+        if not self.eps_fn:
+            return None
+        frames = self.engine.vits_frames(G, speed)
+        return self.eps_fn(G) if frames == 2 * G else self.eps_fn(G, frames)
+
     def next_seed(self):
         """Seed of the next call's noise (None in zero mode)."""
         if self.noise == "zero":
@@ -219,7 +231,9 @@ class VitsSession(_Session):
         f = input_feed
         self._need(f, "text_seq", "pred_semantic")
         sem = np.asarray(f["pred_semantic"]).reshape(-1)
-        eps = self.eps_fn(sem.size) if self.eps_fn else None
+        speed = f.get("speed")
+        speed = 1.0 if speed is None else float(np.asarray(speed).reshape(-1)[0])
+        eps = self.eps(sem.size, speed)
         seed = None if eps is not None else self.next_seed()
         if self.version == "v2":
             self._need(f, "ref_audio")
@@ -228,7 +242,7 @@ class VitsSession(_Session):
             self._need(f, "ge", "ge_advanced")
             cond = dict(ge=f["ge"], ge_advanced=f["ge_advanced"])
         audio = self.engine.vits_decode(f["text_seq"], sem, eps=eps, noise_scale=self.noise_scale, noise_seed=seed,
-                                        **cond)
+                                        speed=speed, **cond)
         return self._select(output_names, {"audio": _np(audio)})
 
 

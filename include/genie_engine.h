@@ -159,7 +159,7 @@ int gsv_t2s_read_kv(gsv_engine* eng, int seq, int layer, float* k, float* v, int
  *     ge (device [512]) from gsv_ref_encode of that audio (identical output).
  * V2ProPlus: ge (device [1024]), ge_adv (device [512]), ref_audio NULL.
  * eps: (device [192, 2*n_sem]) noise for z_p, or NULL => zeros.
- * audio (device f32 [640*2*n_sem]). */
+ * audio (device f32 [640*2*n_sem]).  Speech rate 1; gsv_vits_decode_item takes a rate. */
 int gsv_vits_decode(gsv_engine* eng, const int64_t* text_seq, int32_t n_text,
                     const int64_t* sem, int32_t n_sem, const float* ref_audio, int32_t n_audio,
                     const float* ge, const float* ge_adv, const float* eps, float noise_scale,
@@ -179,7 +179,27 @@ int gsv_vits_decode(gsv_engine* eng, const int64_t* text_seq, int32_t n_text,
  * gsv_vits_decode.
  * Noise for z_p (vits(v2)#6490 RandomNormalLike x noise_scale):
  *   noise_mode 0: zeros; 1: eps (device [192, 2*n_sem]); 2: the engine's Philox
- *   N(0,1) stream keyed by noise_seed (counter = element index; Box-Muller). */
+ *   N(0,1) stream keyed by noise_seed (counter = element index; Box-Muller).
+ *
+ * Speech rate (`speed`, GPT-SoVITS TextEncoder.forward's argument; the ONNX graphs were
+ * exported with it fixed at 1): the 192-channel latent is resampled linearly along time
+ * between enc_p.encoder2 and enc_p.proj, from T = 2*n_sem to T' frames, and proj, the noise,
+ * the reverse flows and the generator run at T'.  Pitch is unchanged; the audio is
+ * 640 * T' samples.
+ *   T' = gsv_vits_frames(n_sem, speed): T when speed == 0 or 1 (a zero-initialised item
+ *   means "as before"), else (int)((double)T / (double)speed) + 1 -- the float32 speed
+ *   widened to double, so callers take T' from gsv_vits_frames and never recompute it
+ *   (n_sem = 11: the double 1.1 gives 21, the float32 1.1 gives 20).  Valid: finite,
+ *   0.25 <= speed <= 4 (else GSV_E_ARG; gsv_vits_frames returns GSV_E_ARG);
+ *   T' > 4096 is GSV_E_CAPACITY (the generator workspace grows with T').
+ *   Resample (ATen's align_corners = False formula in float32, every multiply and add rounded
+ *   on its own): scale = (float)T / (float)T'; src = max(scale * (j + 0.5f) - 0.5f, 0);
+ *   i0 = min((int)src, T-1); i1 = i0 + (i0 < T-1); l1 = src - i0; l0 = 1 - l1;
+ *   out[c][j] = l0 * y[c][i0] + l1 * y[c][i1].
+ *   eps is [192, T'] then, and the Philox counter is the element index over 192 * T'.
+ * In a batch every item has its own speed.  The segmented generator pass lays the
+ * utterances out by T'_i; the packed front ("seg_front") is used only when every item's
+ * T' equals its T, otherwise the fronts run per item on the lanes. */
 typedef struct {
     const int64_t* text_seq; int32_t n_text;   /* device */
     const int64_t* sem;      int32_t n_sem;    /* device */
@@ -189,8 +209,14 @@ typedef struct {
     const float* eps;                          /* noise_mode 1 */
     uint64_t noise_seed;                       /* noise_mode 2 */
     int32_t noise_mode;
-    float* audio;                              /* device [1280 * n_sem] */
+    float* audio;                              /* device [640 * gsv_vits_frames(n_sem, speed)] */
+    float speed;                               /* speech rate, 0 == 1.0 (see above) */
 } gsv_vits_item;
+int gsv_vits_frames(int32_t n_sem, float speed);
+/* One utterance, synchronously, as gsv_vits_decode but described by an item (so with its
+ * speed and noise_mode 2).  Bit-identical to gsv_vits_decode for speed 0 or 1 and
+ * noise_mode 0 or 1. */
+int gsv_vits_decode_item(gsv_engine* eng, const gsv_vits_item* item, float noise_scale, void* stream);
 int gsv_vits_decode_batch(gsv_engine* eng, int32_t n, const gsv_vits_item* items, float noise_scale,
                           void* stream);
 
@@ -318,6 +344,8 @@ int gsv_debug_copy(gsv_engine* eng, const char* name, float* dst, int64_t n, voi
 int gsv_debug_conv1d(const float* x, int cin, int tin, const float* w, int cout, int k, int dil,
                      int pad, const float* bias, float* out, int tout, int in_act, float slope,
                      float* splitk_ws, int64_t splitk_cap, void* stream);
+/* The speech-rate resample alone: x (device [c][t]) -> out (device [c][t_out]). */
+int gsv_debug_interp_linear(const float* x, int c, int t, int t_out, float* out, void* stream);
 /* The same conv on the f16-split MFMA path (vits_convh.hip, the MRF convs of
  * dec.resblocks.* in vits_fp32.onnx): wh = fp16 weights [cout][k][cin], scale =
  * per-output-channel f32 factor on the sums (weight norm g/||v||); *ovf (device
