@@ -241,6 +241,28 @@ def _rate(speed) -> dict:
     return {} if float(speed) == 1.0 else {"speed": float(speed)}
 
 
+def _sampling(top_k=None, top_p=None, temperature=None, repetition_penalty=None, seed=None) -> dict:
+    """The sampling keywords of a synthesis call that were given, validated (ValueError for
+    a value the engine rejects) before anything is synthesized."""
+    from .engine import check_sampling
+    return check_sampling(top_k=top_k, top_p=top_p, temperature=temperature,
+                          repetition_penalty=repetition_penalty, seed=seed)
+
+
+def _resolve_sampler(character_name: str, sampler, fields: dict):
+    """The sampler of a call: `sampler` as passed when no keyword overrides a field (today's
+    call, unchanged), else a copy of it -- or of the character's own -- with those fields set."""
+    if not fields:
+        return sampler
+    from .engine import override_sampler
+    if sampler is None:
+        m = model_manager.get(character_name)
+        if m is None:
+            raise ValueError(f"character '{character_name}' is not loaded")
+        sampler = m.T2S_FIRST_STAGE_DECODER.sampler
+    return override_sampler(sampler, **fields)
+
+
 def _synthesize(character_name: str, sentence, text_bert=None, sampler=None, speed: float = 1.0) -> np.ndarray:
     m = model_manager.get(character_name)
     if m is None:
@@ -290,15 +312,22 @@ def _play(audio: np.ndarray) -> None:
 
 def tts(character_name: str, text: Union[str, Sequence[int], np.ndarray], play: bool = False,
         split_sentence: bool = True, save_path: Union[str, os.PathLike, None] = None,
-        text_bert: Optional[np.ndarray] = None, sampler=None, speed: float = 1.0) -> Optional[np.ndarray]:
+        text_bert: Optional[np.ndarray] = None, sampler=None, speed: float = 1.0, *,
+        top_k: Optional[int] = None, top_p: Optional[float] = None, temperature: Optional[float] = None,
+        repetition_penalty: Optional[float] = None, seed: Optional[int] = None) -> Optional[np.ndarray]:
     """Internal.py:265-310 (TTSPlayer session: split, synthesize each sentence, save the
     concatenation as 16-bit WAV).  Returns the audio f32 [sum 1280*G_i] at 32 kHz.
     speed: the speech rate (GPT-SoVITS's `speed`, 0.25 .. 4; ValueError otherwise): sentence i
-    is 640 * Engine.vits_frames(G_i, speed) samples, its pitch unchanged."""
+    is 640 * Engine.vits_frames(G_i, speed) samples, its pitch unchanged.
+    top_k (1..64), top_p (0 < p <= 1, nucleus sampling), temperature (> 0), repetition_penalty
+    (> 0), seed: GPT-SoVITS's sampling controls; None keeps the field of `sampler` (or, without
+    one, of the character's sampler), a value overrides it on a copy.  ValueError for a bad value."""
     rate = _rate(speed)
+    fields = _sampling(top_k, top_p, temperature, repetition_penalty, seed)
     if character_name not in _reference_audios:
         logger.error("Please call 'set_reference_audio' first to set the reference audio.")
         return None
+    sampler = _resolve_sampler(character_name, sampler, fields)
     _session_stop.clear()                    # TTSPlayer.start_session
     chunks = [c for c in _synthesize_all(character_name, _sentences(text, split_sentence), text_bert, sampler,
                                          **rate)
@@ -314,20 +343,26 @@ def tts(character_name: str, text: Union[str, Sequence[int], np.ndarray], play: 
 
 
 async def tts_async(character_name: str, text: str, play: bool = False, split_sentence: bool = False,
-                    save_path: Union[str, os.PathLike, None] = None, speed: float = 1.0) -> AsyncIterator[bytes]:
+                    save_path: Union[str, os.PathLike, None] = None, speed: float = 1.0, *, sampler=None,
+                    top_k: Optional[int] = None, top_p: Optional[float] = None,
+                    temperature: Optional[float] = None, repetition_penalty: Optional[float] = None,
+                    seed: Optional[int] = None) -> AsyncIterator[bytes]:
     """Internal.py:193-262: yields one raw 16-bit PCM chunk per sentence as soon as it
     is synthesized (TTSPlayer chunk callback), the engine running off the event loop.
-    speed: as for tts."""
+    speed, sampler and the sampling keywords: as for tts."""
     rate = _rate(speed)
+    fields = _sampling(top_k, top_p, temperature, repetition_penalty, seed)
     if character_name not in _reference_audios:
         raise ValueError("Please call 'set_reference_audio' first to set the reference audio.")
+    sampler = _resolve_sampler(character_name, sampler, fields)
     loop = asyncio.get_running_loop()
     _session_stop.clear()                    # TTSPlayer.start_session
     chunks = []
     for s in _sentences(text, split_sentence):
         if _session_stop.is_set():
             return
-        audio = await loop.run_in_executor(None, functools.partial(_synthesize, character_name, s, **rate))
+        audio = await loop.run_in_executor(None, functools.partial(_synthesize, character_name, s, sampler=sampler,
+                                                                     **rate))
         if _session_stop.is_set():
             # stop() during the sentence: the reference's worker sends chunk_callback(None) and
             # the iterator ends without that chunk (TTSPlayer.py:109-114, Internal.py:258-262)

@@ -47,6 +47,14 @@ int set_error(int code, const std::string& msg) {
 int hip_error(const std::string& what, hipError_t e) {
     return set_error(GSV_E_HIP, what + ": " + hipGetErrorName(e));
 }
+
+// The range checks every sampler-taking entry point makes (null: the defaults).
+int check_sampler(const gsv_sampler* s) {
+    if (!s) return 0;
+    if (s->top_k < 1 || s->top_k > 64) return set_error(GSV_E_ARG, "top_k must be in [1, 64]");
+    if (!(s->top_p >= 0.f && s->top_p <= 1.f)) return set_error(GSV_E_ARG, "top_p must be in (0, 1]");
+    return 0;
+}
 }  // namespace gsv
 
 // ------------------------------------------------------------ allocation
@@ -867,6 +875,7 @@ SampleArgs gsv_engine::sampler_args(const gsv_sampler* sp, int B) {
     sa.top_k = sp ? sp->top_k : 15;
     sa.temperature = sp ? sp->temperature : 1.0f;
     sa.rep_penalty = sp ? sp->repetition_penalty : 1.35f;
+    sa.top_p = sp ? norm_top_p(sp->top_p) : 1.0f;
     sa.greedy = sp ? sp->greedy : 1;
     sa.seed = sp ? sp->seed : 0;
     sa.max_steps = sp ? sp->max_steps : 500;
@@ -986,7 +995,8 @@ hipGraphExec_t gsv_engine::step_graph(int B, const gsv_sampler* sp, int chunk, h
                             std::to_string(sp->seed) + ":" + std::to_string(sp->max_steps) + ":" +
                             std::to_string(sp->force_steps) + ":" +
                             std::to_string(sp->temperature) + ":" +
-                            std::to_string(sp->repetition_penalty);
+                            std::to_string(sp->repetition_penalty) + ":" +
+                            std::to_string(__builtin_bit_cast(uint32_t, norm_top_p(sp->top_p)));
     auto it = graphs.find(key);
     if (it != graphs.end()) return it->second;
     hipGraph_t g = nullptr;
@@ -1189,6 +1199,7 @@ int gsv_engine::persist_enqueue(int B, const gsv_sampler* sp, hipStream_t st, in
     a.seen = seen + (size_t)slot * 33;
     a.top_k = sp->top_k; a.temperature = sp->temperature; a.rep_penalty = sp->repetition_penalty;
     a.greedy = sp->greedy; a.seed = sp->seed; a.max_steps = sp->max_steps; a.force_steps = sp->force_steps;
+    a.top_p = norm_top_p(sp->top_p);
     a.force_b = forceb + slot;
     a.ring = (unsigned long long*)pws;
     a.epoch = pepoch;
@@ -1374,12 +1385,14 @@ bool same_utt(const gsv_utt& a, const gsv_utt& b) {
 }
 bool same_sampler(const gsv_sampler& a, const gsv_sampler& b) {
     return a.top_k == b.top_k && a.temperature == b.temperature && a.repetition_penalty == b.repetition_penalty &&
-           a.greedy == b.greedy && a.seed == b.seed && a.max_steps == b.max_steps && a.force_steps == b.force_steps;
+           a.greedy == b.greedy && a.seed == b.seed && a.max_steps == b.max_steps && a.force_steps == b.force_steps &&
+           norm_top_p(a.top_p) == norm_top_p(b.top_p);
 }
 // the sampler generate runs with (defaults of the reference graphs)
 int norm_sampler(const gsv_sampler* s, gsv_sampler& sp) {
     sp = s ? *s : gsv_sampler{15, 1.0f, 1.35f, 1, 0, 500, 0};
-    if (sp.top_k < 1 || sp.top_k > 64) return set_error(GSV_E_ARG, "top_k must be in [1, 64]");
+    if (int e = check_sampler(&sp)) return e;
+    sp.top_p = norm_top_p(sp.top_p);
     if (sp.max_steps <= 0) sp.max_steps = 500;
     return 0;
 }
@@ -1614,7 +1627,7 @@ extern "C" int gsv_t2s_prefill(gsv_engine* eng, int seq, const float* x, int32_t
     if (int e = eng->pf_drop()) return e;   // a prefetch writes the T2S workspaces and slot 1
     if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
     if (seq < 0 || seq >= eng->max_batch) return set_error(GSV_E_CAPACITY, "slot out of range");
-    if (s && (s->top_k < 1 || s->top_k > 64)) return set_error(GSV_E_ARG, "top_k must be in [1, 64]");
+    if (int e = check_sampler(s)) return e;
     StreamScope sc(eng, stream);
     hipStream_t st = sc.st();
     if (int e = eng->prefill_slot(seq, x, n_x, prompts, n_prompts, s, logits_out, st)) return e;
@@ -1635,7 +1648,7 @@ extern "C" int gsv_t2s_decode_steps(gsv_engine* eng, int seq, int nsteps, const 
     StreamScope sc(eng, stream);
     hipStream_t st = sc.st();
     gsv_sampler sp = s ? *s : gsv_sampler{15, 1.0f, 1.35f, 1, 0, 500, 0};
-    if (sp.top_k < 1 || sp.top_k > 64) return set_error(GSV_E_ARG, "top_k must be in [1, 64]");
+    if (int e = check_sampler(&sp)) return e;
     sp.force_steps = 1 << 30;   // session semantics: the caller owns the stop decision
     hipMemsetAsync(eng->done, 0, 1, st);
     hipMemsetAsync(eng->forceb, 0, 4, st);
@@ -1984,7 +1997,7 @@ extern "C" int gsv_get_timing(gsv_engine* eng, float* ms4) {
 extern "C" int gsv_debug_sample(const float* logits, const uint32_t* seen, int B, const gsv_sampler* s,
                                 int step, int64_t* tokens, uint8_t* stop, void* stream) {
     if (!logits || !seen || !s || !tokens || B <= 0 || step < 1) return set_error(GSV_E_ARG, "bad args");
-    if (s->top_k < 1 || s->top_k > 64) return set_error(GSV_E_ARG, "top_k must be in [1, 64]");
+    if (int e = check_sampler(s)) return e;
     hipStream_t st = (hipStream_t)stream;
     // scratch decode state: y[b] (ldy 1), ny = 0, steps = step - 1, done = 0
     char* buf = nullptr;
@@ -2004,6 +2017,7 @@ extern "C" int gsv_debug_sample(const float* logits, const uint32_t* seen, int B
     a.B = B; a.logits = logits; a.ldl = 1025; a.y = y; a.ldy = 1; a.ny = ny; a.seen = seen_c;
     a.done = done; a.stop_out = stop; a.steps = steps; a.kvlen = kvlen;
     a.top_k = s->top_k; a.temperature = s->temperature; a.rep_penalty = s->repetition_penalty;
+    a.top_p = norm_top_p(s->top_p);
     a.greedy = s->greedy; a.seed = s->seed; a.max_steps = 1 << 30; a.force_steps = 0; a.prefill = 0;
     sample_tokens(a, st);
     hipMemcpyAsync(tokens, y, (size_t)B * 8, hipMemcpyDeviceToDevice, st);

@@ -19,6 +19,8 @@
 
 namespace gsv {
 int set_error(int code, const std::string& msg);
+int check_sampler(const gsv_sampler* s);   // top_k in [1, 64], top_p in (0, 1] or 0 (unset)
+inline float norm_top_p(float p) { return p == 0.f ? 1.f : p; }   // gsv_sampler.top_p: 0 means 1
 int hip_error(const std::string& what, hipError_t e);   // GSV_E_HIP, the message naming the HIP error
 int f16_inexact_error(const std::string& weight, const float* v, int64_t index);
 struct StreamScope;

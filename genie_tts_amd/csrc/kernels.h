@@ -214,6 +214,7 @@ struct SampleArgs {
     int* steps;                        // per-b executed loop steps
     int* kvlen;                        // per-b KV length, +1 per executed step
     int top_k; float temperature; float rep_penalty;
+    float top_p;                       // nucleus cut, (0, 1]; 1 = off (the host maps 0 to 1)
     int greedy; uint64_t seed;
     int max_steps; int force_steps;
     const int* force_b;                // optional per-sequence force_steps (>0 overrides force_steps)
@@ -251,6 +252,7 @@ struct PersistArgs {
     long sstride; int tmax; float scale;
     int64_t* y; long ldy; int* ny; int* kvlen; int* steps; uint8_t* done; uint8_t* stop_out; uint32_t* seen;
     int top_k; float temperature; float rep_penalty; int greedy; uint64_t seed; int max_steps; int force_steps;
+    float top_p;                                  // nucleus cut, (0, 1]; 1 = off (the host maps 0 to 1)
     const int* force_b;                           // optional per-sequence force_steps (>0 overrides)
     unsigned long long* ring;                     // granule ring (persist1_ring_bytes / persist1m_ring_bytes)
     unsigned epoch;                               // launch epoch (tag high bits), 1 .. 2^20-1

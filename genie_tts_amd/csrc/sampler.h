@@ -99,6 +99,116 @@ __device__ __forceinline__ void sort_desc(float (&h)[N]) {
             if (h[j] > h[j - 1]) { const float t = h[j]; h[j] = h[j - 1]; h[j - 1] = t; }
 }
 
+// ---------------------------------------------------------------------
+// Nucleus sampling (top_p < 1; GPT-SoVITS logits_to_probs order): over the PENALISED
+// logits l (before /temperature) p = softmax(l); tokens ordered by l descending, equal
+// l by ascending index; S_i the inclusive cumulative sum of p in that order; token i is
+// removed iff S_i > top_p and i is not first.  The survivors are a prefix of the order,
+// so one cut key describes them: i survives iff topp_key(l_i, i) >= cut.
+//
+// Exact for any survivor count: all 1025 (value, index) keys, padded with zeros to
+// TOPP_N, are sorted descending by a block bitonic sort in `srt` (TOPP_N u64 = 16 KB of
+// LDS, 66 stages of one barrier each), exp(l - max) is taken in sorted order and scanned
+// in ONE fixed order whatever NT is (512 runs of 4 consecutive elements summed serially,
+// a wave inclusive scan over each 64 runs, the 8 wave totals added serially), so every
+// path gives the same cut bit for bit.  The cut is the first position r >= 1 with
+// S_r > top_p * S_total (an integer minimum: a prefix even if rounding made S dip).
+// Every loop's trip count is fixed by NT / VOCAB / TOPP_N; NaN or inf logits only make
+// comparisons false.
+// ---------------------------------------------------------------------
+#define TOPP_N 2048
+__device__ __forceinline__ unsigned long long topp_key(float l, int i) {
+    // l + 0: -0 orders as +0 (equal values tie on the index); ~i: ascending index first
+    return ((unsigned long long)f2key(l + 0.f) << 32) | (uint32_t)~(uint32_t)i;
+}
+
+// `srt` may alias the caller's logits row: every thread holds its logits in registers
+// and a barrier has passed since the loads.  sv / si: >= 16 floats / ints of LDS.
+template <int NT, int SLOTS>
+__device__ __forceinline__ unsigned long long top_p_cut(const float (&pen)[SLOTS], float top_p,
+                                                        unsigned long long* srt, float* sv, int* si) {
+    constexpr int NW = NT / 64;
+    constexpr int RUNS = TOPP_N / 4 / NT;   // runs of 4 elements per thread
+    static_assert(TOPP_N / 4 % NT == 0 && TOPP_N / 4 / 64 <= 16, "scan layout");
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+#pragma unroll
+    for (int j = 0; j < SLOTS; ++j) {
+        const int i = tid + NT * j;
+        if (i < VOCAB) srt[i] = topp_key(pen[j], i);
+    }
+    for (int i = VOCAB + tid; i < TOPP_N; i += NT) srt[i] = 0ull;   // below every real key
+    for (int k = 2; k <= TOPP_N; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            __syncthreads();
+            for (int t = tid; t < TOPP_N / 2; t += NT) {
+                const int lo = 2 * t - (t & (j - 1)), hi = lo + j;
+                const unsigned long long x = srt[lo], y = srt[hi];
+                if ((x < y) == ((lo & k) == 0)) { srt[lo] = y; srt[hi] = x; }
+            }
+        }
+    }
+    __syncthreads();
+    const float mx = key2f((uint32_t)(srt[0] >> 32));
+    float c[RUNS][4], excl[RUNS];
+#pragma unroll
+    for (int q = 0; q < RUNS; ++q) {
+        const int r0 = 4 * (tid + NT * q);
+        float run = 0.f;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float e = r0 + u < VOCAB ? expf(key2f((uint32_t)(srt[r0 + u] >> 32)) - mx) : 0.f;
+            run += e;
+            c[q][u] = run;
+        }
+        float inc = run;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const float up = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += up;
+        }
+        const float prev = __shfl_up(inc, 1, 64);
+        excl[q] = lane ? prev : 0.f;
+        if (lane == 63) sv[w + NW * q] = inc;   // total of runs [64 (w + NW q), + 64)
+    }
+    __syncthreads();
+    float total = 0.f;
+#pragma unroll
+    for (int g = 0; g < TOPP_N / 4 / 64; ++g) total += sv[g];
+    const float lim = top_p * total;
+    int cut = VOCAB;
+#pragma unroll
+    for (int q = 0; q < RUNS; ++q) {
+        const int r0 = 4 * (tid + NT * q), wg = w + NW * q;
+        float base = 0.f;
+#pragma unroll
+        for (int g = 0; g < TOPP_N / 4 / 64; ++g)
+            if (g < wg) base += sv[g];
+        base += excl[q];
+#pragma unroll
+        for (int u = 3; u >= 0; --u)
+            if (r0 + u >= 1 && r0 + u < VOCAB && base + c[q][u] > lim) cut = min(cut, r0 + u);
+    }
+    cut = wave_min_dpp(cut);
+    if (lane == 0) si[w] = cut;
+    __syncthreads();
+    cut = si[0];
+#pragma unroll
+    for (int k = 1; k < NW; ++k) cut = min(cut, si[k]);
+    return srt[cut - 1];
+}
+
+// top_p_cut as a real (not inlined, cold) call: the persistent kernels sit at the 256-VGPR
+// limit, and inlined the sort and scan changed the register allocation of their layer
+// loops (more spills on the path every step takes).  As a call, the code a launch without
+// top_p runs keeps its allocation; the saves around the call run only when top_p < 1.
+template <int SLOTS>
+struct PenV { float v[SLOTS]; };   // by value: the penalised logits travel in registers
+template <int NT, int SLOTS>
+__device__ __attribute__((noinline, cold)) unsigned long long top_p_cut_call(PenV<SLOTS> pen, float top_p,
+                                                                       unsigned long long* srt, float* sv, int* si) {
+    return top_p_cut<NT>(pen.v, top_p, srt, sv, si);
+}
+
 // Shared LDS of one block-sampler invocation (NT threads).
 template <int NT>
 struct SampleLds {
@@ -111,11 +221,13 @@ struct SampleLds {
 // One sequence's sampling decision on NT threads (the whole block participates).
 // ld(i) returns logit i (i < VOCAB); seen_s is the presence bitmap (33 words, LDS);
 // step is the 1-based loop step fed to Philox (0 for the first stage).  Returns the
-// token (uniform); *raw_out = argmax of the raw logits (stop rule).
+// token (uniform); *raw_out = argmax of the raw logits (stop rule).  top_p < 1 (sampled
+// mode only: the maximum always survives, so greedy ignores it) runs top_p_cut in srt
+// (TOPP_N u64 of LDS; unused otherwise).
 template <int NT, typename LoadF>
 __device__ int sample_block(LoadF ld, const uint32_t* seen_s, int b, int step, int top_k, float temperature,
-                            float rep_penalty, int greedy, uint64_t seed, int ablate, float* logits_out,
-                            int* raw_out, SampleLds<NT>& sh) {
+                            float rep_penalty, float top_p, int greedy, uint64_t seed, int ablate,
+                            float* logits_out, int* raw_out, SampleLds<NT>& sh, unsigned long long* srt) {
     constexpr int SLOTS = (VOCAB + NT - 1) / NT;
     constexpr int NW = NT / 64;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -154,9 +266,23 @@ __device__ int sample_block(LoadF ld, const uint32_t* seen_s, int b, int step, i
             if (i < VOCAB) argmax_merge(gv, gi, v[j], i);
         }
         block_argmax_dpp(gv, gi, sh.sv, sh.si);
-        return gi;
+        return min(gi, VOCAB - 1);   // an all-NaN row (see the end of this function)
     }
     if (ablate == 3) return ri;
+    if (__builtin_expect(top_p < 1.f, 0)) {
+        PenV<SLOTS> pen;
+#pragma unroll
+        for (int j = 0; j < SLOTS; ++j) {
+            const int i = tid + NT * j;
+            pen.v[j] = l[j];
+            if (i < VOCAB && ((seen_s[i >> 5] >> (i & 31)) & 1u))
+                pen.v[j] = l[j] < 0.f ? l[j] * rep_penalty : l[j] / rep_penalty;
+        }
+        const unsigned long long cut = top_p_cut_call<NT, SLOTS>(pen, top_p, srt, sh.sv, sh.si);
+#pragma unroll
+        for (int j = 0; j < SLOTS; ++j)
+            if (topp_key(pen.v[j], tid + NT * j) < cut) v[j] = -INFINITY;
+    }
     const int K = top_k;
     // ---- k-th largest with multiplicity: every wave extracts its own k largest (one
     // instance per round), then wave 0 extracts the k-th largest of the NW*k candidates.
@@ -214,7 +340,10 @@ __device__ int sample_block(LoadF ld, const uint32_t* seen_s, int b, int step, i
         argmax_merge(bv, bi, p / q, i);
     }
     block_argmax_dpp(bv, bi, sh.sv, sh.si);
-    return bi;
+    // Non-finite logits (NaN, or +inf: exp(inf - inf)) make every p / q NaN: no candidate ever
+    // compares, the index stays 0x7fffffff and the callers' seen[tok >> 5] update would write
+    // ~256 MB out of bounds.  Such a row yields EOS; finite rows always give bi < VOCAB.
+    return min(bi, VOCAB - 1);
 }
 
 }  // namespace gsv

@@ -1521,6 +1521,7 @@ template <int NT>
 __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
     __shared__ SampleLds<NT> sh;
     __shared__ uint32_t seen_s[33];
+    __shared__ unsigned long long srt[TOPP_N];   // top_p < 1: the sort space of top_p_cut
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* lg = a.logits + (long)b * a.ldl;
     const uint32_t* seen = a.seen + (long)b * 33;
@@ -1551,8 +1552,8 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
     const int step = a.prefill ? 0 : step_s + 1;
     int raw = 0;
     const int tok = sample_block<NT>([&](int i) { return lg[i]; }, seen_s, a.b0 + b, step, a.top_k, a.temperature,
-                                     a.rep_penalty, a.greedy, a.seed, a.ablate,
-                                     a.logits_out ? a.logits_out + (long)b * a.ldlo : nullptr, &raw, sh);
+                                     a.rep_penalty, a.top_p, a.greedy, a.seed, a.ablate,
+                                     a.logits_out ? a.logits_out + (long)b * a.ldlo : nullptr, &raw, sh, srt);
     if (tid == 0) {
         if (a.ablate == 3) { a.y[(long)b * a.ldy + st_ny] = raw; a.ny[b] = st_ny + 1; return; }
         sample_commit(a, b, tok, raw, st_ny, st_steps, st_kv, seen_s);

@@ -215,6 +215,13 @@ struct Shared1 {
     } m;
 };
 
+// top_p_cut's sort space: the score array, idle between a step's last attention pass and
+// the next step's first (K / V hold the next layer's LDS-DMA prefetch then, lg the logits)
+static_assert(sizeof(Shared1::at.p) >= TOPP_N * 8 && offsetof(Shared1, at.p) % 8 == 0, "top_p sort space");
+__device__ __forceinline__ unsigned long long* topp_space(Shared1& sh) {
+    return reinterpret_cast<unsigned long long*>(sh.at.p);
+}
+
 #define STAMP1(i)                                                                         \
     do {                                                                                  \
         if (probe && threadIdx.x == 0) {                                                  \
@@ -963,7 +970,8 @@ __device__ void run_attn(const PersistArgs& a, const Ws1& ws, Shared1& sh, int g
                 if (!block_ok1(ok, sh)) return;
                 STAMP1(1);
                 tok = sample_block<PT>([&](int i) { return sh.at.lg[i]; }, sh.seen, 0, st + 1, a.top_k,
-                                       a.temperature, a.rep_penalty, a.greedy, a.seed, 0, nullptr, &raw, sh.samp);
+                                       a.temperature, a.rep_penalty, a.top_p, a.greedy, a.seed, 0, nullptr, &raw,
+                                       sh.samp, topp_space(sh));
             }
             if (tid == 0) {
                 a.y[ny0 + s] = tok;
@@ -1667,8 +1675,8 @@ __device__ void run_attn_m(const PersistArgs& a, const WsSeq& base, Shared1& sh,
                 uint32_t* seen = sh.m.seens[b >> 4];
                 int raw = 0;
                 const int tok = sample_block<PT>([&](int i) { return sh.at.lg[i]; }, seen, b, st + 1, a.top_k,
-                                                 a.temperature, a.rep_penalty, a.greedy, a.seed, 0, nullptr, &raw,
-                                                 sh.samp);
+                                                 a.temperature, a.rep_penalty, a.top_p, a.greedy, a.seed, 0, nullptr,
+                                                 &raw, sh.samp, topp_space(sh));
                 if (tid == 0) {
                     const int stop = (raw == 1024 || tok == 1024) ? 1 : 0;
                     const int fin = seq_finished(a.force_b, b, a.force_steps, a.max_steps, st + 1, stop) ? 1 : 0;

@@ -54,6 +54,9 @@ struct SharedM {
             } g;
             float pk[MG][512];                // the rows a pass publishes
             float lg[1056];                   // sampler: one sequence's logits
+            uint32_t srt[2 * TOPP_N];         // sampler, top_p < 1: top_p_cut's sort space, TOPP_N u64 keys
+                                              // (over lg: the logits are in registers by then; 32-bit
+                                              // words so the struct keeps its size, `sh` is 16-byte aligned)
         };
     } at;
     _Float16 F[2 * MG][FST];                  // FFN2's A tile (FFN1 outputs)
@@ -1140,7 +1143,8 @@ __device__ void run_group(const PersistArgs& a, const WsSeq& base, SharedM& sh, 
             uint32_t* seen = sh.seenq[i];
             int raw = 0;
             const int tok = sample_block<PT>([&](int k) { return sh.at.lg[k]; }, seen, b, st + 1, a.top_k,
-                                             a.temperature, a.rep_penalty, a.greedy, a.seed, 0, nullptr, &raw, sh.samp);
+                                             a.temperature, a.rep_penalty, a.top_p, a.greedy, a.seed, 0, nullptr, &raw,
+                                             sh.samp, reinterpret_cast<unsigned long long*>(sh.at.srt));
             if (tid == 0) {
                 const int stop = (raw == 1024 || tok == 1024) ? 1 : 0;
                 const int fin = seq_finished(a.force_b, b, a.force_steps, a.max_steps, st + 1, stop) ? 1 : 0;
@@ -1189,7 +1193,8 @@ __device__ void run_group(const PersistArgs& a, const WsSeq& base, SharedM& sh, 
 }
 
 __global__ __launch_bounds__(PT) void k_decode_persistm(PersistArgs a) {
-    __shared__ SharedM sh;
+    __shared__ alignas(16) SharedM sh;
+    static_assert(offsetof(SharedM, at.srt) % 8 == 0 && sizeof(SharedM::at.srt) == TOPP_N * 8, "top_p sort space");
     WsSeq ws;
     ws.ring = a.ring;
     ws.epoch = a.epoch;

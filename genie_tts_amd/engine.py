@@ -8,6 +8,7 @@ point raises.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import threading
 import weakref
@@ -89,15 +90,60 @@ class Sampler(ctypes.Structure):
         ("repetition_penalty", ctypes.c_float), ("greedy", ctypes.c_int32),
         ("seed", ctypes.c_uint64), ("max_steps", ctypes.c_int32),
         ("force_steps", ctypes.c_int32),
+        ("top_p", ctypes.c_float),
     ]
+
+
+SAMPLING_FIELDS = ("top_k", "top_p", "temperature", "repetition_penalty", "seed")
+
+
+def check_sampling(top_k=None, top_p=None, temperature=None, repetition_penalty=None, seed=None) -> dict:
+    """The sampling controls of a request (None: not given), validated: top_k 1..64,
+    0 < top_p <= 1, temperature > 0, repetition_penalty > 0, seed a 64-bit unsigned integer.
+    ValueError otherwise.  Returns the given ones as Sampler field values."""
+    out = {}
+    if top_k is not None:
+        if isinstance(top_k, bool) or int(top_k) != top_k or not 1 <= int(top_k) <= 64:
+            raise ValueError(f"top_k must be an integer in [1, 64], got {top_k!r}")
+        out["top_k"] = int(top_k)
+    for name, v, hi in (("top_p", top_p, 1.0), ("temperature", temperature, math.inf),
+                        ("repetition_penalty", repetition_penalty, math.inf)):
+        if v is None:
+            continue
+        v = float(v)
+        if not (0.0 < v <= hi) or not math.isfinite(v):
+            raise ValueError(f"{name} must be in (0, 1], got {v!r}" if name == "top_p"
+                             else f"{name} must be a finite number > 0, got {v!r}")
+        out[name] = v
+    if seed is not None:
+        if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 1 << 64:
+            raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+        out["seed"] = int(seed)
+    return out
+
+
+def override_sampler(base: Sampler, **fields) -> Sampler:
+    """A copy of `base` with the given (validated) sampling fields replaced."""
+    sp = Sampler.from_buffer_copy(base)
+    for k, v in check_sampling(**fields).items():
+        setattr(sp, k, v)
+    return sp
+
+
+def sampler_key(sp: Sampler) -> tuple:
+    """Every field of a sampler (top_p 0 read as 1): equal keys sample alike."""
+    return tuple(1.0 if (n == "top_p" and getattr(sp, n) == 0) else getattr(sp, n) for n, _ in Sampler._fields_)
 
 
 def make_sampler(top_k: int = 15, temperature: float = 1.0, repetition_penalty: float = 1.35,
                  greedy: bool = True, seed: int = 1234, max_steps: int = 500,
-                 force_steps: int = 0) -> Sampler:
+                 force_steps: int = 0, top_p: float = 1.0) -> Sampler:
     """Defaults are the constants baked into the reference graphs
-    (t2s_stage_decoder_fp32.onnx#1780-1790, Inference.py:95)."""
-    return Sampler(top_k, temperature, repetition_penalty, int(greedy), seed, max_steps, force_steps)
+    (t2s_stage_decoder_fp32.onnx#1780-1790, Inference.py:95).  top_p: the nucleus cut of
+    GPT-SoVITS (0 < top_p <= 1, ValueError otherwise; 1: off, as the graphs were exported);
+    sampled decoding only (include/genie_engine.h)."""
+    check_sampling(top_p=top_p)
+    return Sampler(top_k, temperature, repetition_penalty, int(greedy), seed, max_steps, force_steps, float(top_p))
 
 
 def lib():

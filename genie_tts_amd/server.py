@@ -58,7 +58,8 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
     import numpy as np
     import genie_tts_amd as genie
     from genie_tts_amd import api, audio as A
-    from genie_tts_amd.engine import make_sampler, vits_frames
+    from genie_tts_amd.engine import (SAMPLING_FIELDS, check_sampling, make_sampler, override_sampler, sampler_key,
+                                      vits_frames)
     from genie_tts_amd.inference import tts_client
     from genie_tts_amd.model_manager import model_manager
     from genie_tts_amd.text_splitter import TextSplitter
@@ -119,9 +120,24 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
         except (TypeError, ValueError) as e:
             reply(kind="error", id=msg["id"], detail=f"speed: {e}")
             return
-        pending.append({"id": msg["id"], "character_name": msg["character_name"], "sentences": sents, "next": 0,
-                        "force_steps": int(msg.get("force_steps") or 0), "save_path": msg.get("save_path"),
-                        "chunks": [], "speed": speed})
+        try:                          # likewise a bad sampling control (top_k, top_p, temperature, ...)
+            sampling = check_sampling(**{k: msg.get(k) for k in SAMPLING_FIELDS})
+        except (TypeError, ValueError) as e:
+            reply(kind="error", id=msg["id"], detail=f"sampling: {e}")
+            return
+        r = {"id": msg["id"], "character_name": msg["character_name"], "sentences": sents, "next": 0,
+             "force_steps": int(msg.get("force_steps") or 0), "save_path": msg.get("save_path"),
+             "chunks": [], "speed": speed, "sampling": sampling, "sampler": None}
+        resolve_sampler(r, model_manager.get(r["character_name"]))
+        pending.append(r)
+
+    def resolve_sampler(r: dict, m) -> None:
+        """r["sampler"]: the character's sampler with the request's sampling controls set, or None
+        for a request without any (the character's own, as before).  Resolved on arrival when
+        the character is loaded, else by the request's first round."""
+        if r["sampling"] and r["sampler"] is None and m is not None:
+            base = m.T2S_FIRST_STAGE_DECODER.sampler or make_sampler(greedy=False)
+            r["sampler"] = override_sampler(base, **r["sampling"])
 
     inflight: List[tuple] = []      # [(group, sentence indexes, wavs, engine)] of the overlapped vocoder
 
@@ -157,7 +173,9 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
                 reply(kind="end", id=r["id"])
 
     def run_round() -> None:
-        """The next sentence of up to MAX_BATCH pending requests of one character.  With
+        """The next sentence of up to MAX_BATCH pending requests of one character and one sampler
+        (a batched generate takes one: requests whose sampling controls differ from the first
+        ready request's wait for a later round).  With
         cfg["pipeline"] this round's T2S runs beside the previous round's vocoder
         (gsv_vits_decode_batch_async), whose chunks are streamed once this T2S is done; with
         nothing left to start, the vocoder is joined at once.  Off by default: measured on
@@ -169,10 +187,17 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
             return
         name = ready[0]["character_name"]
         group = [r for r in ready if r["character_name"] == name]
+        m = model_manager.get(name)
+        own = m.T2S_FIRST_STAGE_DECODER.sampler if m is not None else None
+
+        def skey(r):
+            resolve_sampler(r, m)
+            sp = r["sampler"] or own
+            return None if sp is None else sampler_key(sp)
+        group = [r for r in group if skey(r) == skey(group[0])]
         group = group[:round_size(len(group))]
         idx = [r["next"] for r in group]
         try:
-            m = model_manager.get(name)
             ref = api._reference_audios.get(name)
             if m is None or ref is None:
                 raise ValueError("Character not found or reference audio not set.")
@@ -181,7 +206,7 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
                 ts, tb = api._g2p("。" + r["sentences"][r["next"]], m.LANGUAGE)      # Inference.py:27-28
                 items.append((ts, tb, r["force_steps"]))
             tts_client.stop_event.clear()
-            toks = tts_client.tts_batch_t2s(items, ref, m, m.T2S_FIRST_STAGE_DECODER.sampler)
+            toks = tts_client.tts_batch_t2s(items, ref, m, group[0]["sampler"] or own)
             finish_inflight()
             eng = m.ENGINE if getattr(m.VITS, "engine", None) is m.ENGINE else None
             overlapped = pipeline and eng is not None
@@ -422,6 +447,13 @@ def create_app(router: Router):
         force_steps: int = 0          # benchmark knob (random weights never emit EOS); 0 = the reference's rule
         # speech rate (GPT-SoVITS's `speed`): sentence i is 640 * gsv_vits_frames(G_i, speed) samples
         speed: float = Field(1.0, ge=0.25, le=4.0)
+        # GPT-SoVITS's sampling controls; absent: the character's sampler.  Requests batch with
+        # those whose controls are the same.
+        top_k: Optional[int] = Field(None, ge=1, le=64)
+        top_p: Optional[float] = Field(None, gt=0.0, le=1.0)
+        temperature: Optional[float] = Field(None, gt=0.0)
+        repetition_penalty: Optional[float] = Field(None, gt=0.0)
+        seed: Optional[int] = Field(None, ge=0, lt=1 << 64)
 
     def check(res: List[dict]) -> None:
         bad = [r for r in res if r["kind"] == "error"]
@@ -454,13 +486,17 @@ def create_app(router: Router):
     async def tts_endpoint(payload: TTSPayload):
         gen = router.tts(character_name=payload.character_name, text=payload.text,
                          split_sentence=payload.split_sentence, save_path=payload.save_path,
-                         force_steps=payload.force_steps, speed=payload.speed)
+                         force_steps=payload.force_steps, speed=payload.speed,
+                         **{k: v for k, v in (("top_k", payload.top_k), ("top_p", payload.top_p),
+                                              ("temperature", payload.temperature),
+                                              ("repetition_penalty", payload.repetition_penalty),
+                                              ("seed", payload.seed)) if v is not None})
         try:    # surface "not found" as 404 before the stream starts, as the reference does
             first = await gen.__anext__()
         except StopAsyncIteration:
             first = None
         except RuntimeError as e:
-            code = 404 if "not found" in str(e) else 400 if str(e).startswith("speed:") else 500
+            code = 404 if "not found" in str(e) else 400 if str(e).startswith(("speed:", "sampling:")) else 500
             raise HTTPException(status_code=code, detail=str(e))
 
         async def body():

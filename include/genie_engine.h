@@ -113,7 +113,23 @@ typedef struct {
                                                    ragged-batch tests); 0: the sampler's rule */
 } gsv_utt;
 
-/* Sampler (reference constants: t2s_stage_decoder_fp32.onnx#1780-1801). */
+/* Sampler (reference constants: t2s_stage_decoder_fp32.onnx#1780-1801).
+ *
+ * Nucleus sampling (`top_p`, GPT-SoVITS logits_to_probs; the ONNX graphs were exported
+ * with top_p = 1, so they never show it).  All values float32, per sequence and step:
+ *   1. the repetition penalty over the history tokens gives l[0..1025);
+ *   2. only when top_p < 1: p = softmax(l) (before the temperature); the tokens are
+ *      ordered by l descending, equal l by ascending index; S_i is the inclusive
+ *      cumulative sum of p in that order; token i is removed (l_i := -inf) iff
+ *      S_i > top_p and i is not first in the order.  The first token always survives,
+ *      the token that crosses top_p is removed (the mask is not shifted);
+ *   3. l / temperature, the top-k threshold, softmax and argmax(p / q) as without it
+ *      (fewer survivors than top_k: every survivor stays).
+ *   0 < top_p <= 1, or 0 = unset = 1 (a zero-initialised gsv_sampler behaves as
+ *   before); NaN, negative or > 1: GSV_E_ARG.  Greedy decoding ignores top_p (the
+ *   maximum always survives); the first-stage (prefill) sampler applies it too; the
+ *   stop rule (argmax of the raw logits) is unchanged.  With top_p unset or 1 every
+ *   path does exactly the work it did without the field, and the same tokens. */
 typedef struct {
     int32_t top_k;               /* 15 (1..64) */
     float   temperature;         /* 1.0 */
@@ -122,6 +138,7 @@ typedef struct {
     uint64_t seed;               /* Philox key for N(0,1) when !greedy */
     int32_t max_steps;           /* 500 (Inference.py:95) */
     int32_t force_steps;         /* >0: ignore EOS and run exactly this many loop steps */
+    float   top_p;               /* nucleus cut in (0, 1]; 0 == 1.0 == off (see above) */
 } gsv_sampler;
 
 /* Encoder (t2s_encoder_fp32.onnx) for one utterance:
