@@ -326,6 +326,11 @@ int gsv_engine::finalize_t2s() {
     if (const char* e = std::getenv("GENIE_PERSIST1M")) use_persist1m = std::atoi(e) != 0;
     if (const char* e = std::getenv("GENIE_PERSISTM")) use_persistm = std::atoi(e) != 0;
     if (const char* e = std::getenv("GENIE_PRESPLIT")) use_presplit = std::atoi(e) != 0;
+    if (const char* e = std::getenv("GENIE_GEMM_SMALL_NS")) {   // A/B of the small-M ring depth under bench.py
+        const int v = std::atoi(e);
+        gemm_small_ns = v >= 2 && v <= 4 ? v : 0;
+    }
+    if (const char* e = std::getenv("GENIE_VITS_SLAB_FUSE")) vits_slab_fuse = std::atoi(e) != 0;
     if (const char* e = std::getenv("GENIE_CONVH")) use_convh = std::atoi(e) != 0;
     if (const char* e = std::getenv("GENIE_CONVH_WS")) convh_ws = std::max(0, std::min(2, std::atoi(e)));
     if (const char* e = std::getenv("GENIE_VITS_FORK")) vits_fork = std::atoi(e) != 0;
@@ -551,6 +556,7 @@ int gsv_engine::encode(const gsv_utt* u, float* x, int64_t* prompts, hipStream_t
     const int L = u->n_ref + u->n_text, P = u->n_ssl / 2;
     if (L <= 0 || P <= 0) return set_error(GSV_E_ARG, "empty utterance");
     if (int e = ensure_enc_ws(P, L)) return e;
+    const int cus = stream_cus(st);   // GemmArgs::cus (today's encoder GEMMs have f32 weights: no form follows it yet)
     if (do_prompts) {
     // K2: ssl_proj Conv1d(768,768,k2,s2) as GEMM over im2col, then VQ argmin (#2-48)
     ssl_im2col(u->ssl, u->n_ssl, e_im2col, st);
@@ -558,13 +564,13 @@ int gsv_engine::encode(const gsv_utt* u, float* x, int64_t* prompts, hipStream_t
     g.M = P; g.N = 768; g.K = 1536;
     g.A = e_im2col; g.lda = 1536;
     g.W = ssl_w; g.ldw = 1536; g.w_f16 = 0;
-    g.bias = ssl_b; g.C = e_h; g.ldc = 768; g.mode = EPI_STORE;
+    g.bias = ssl_b; g.C = e_h; g.ldc = 768; g.mode = EPI_STORE; g.cus = cus;
     gemm_nt(g, st);
     sumsq_rows(e_h, 768, P, 768, e_hh, st);
     GemmArgs d{};
     d.M = P; d.N = 1024; d.K = 768;
     d.A = e_h; d.lda = 768; d.W = codebook; d.ldw = 768; d.w_f16 = 0;
-    d.C = e_dist; d.ldc = 1024; d.mode = EPI_VQDIST; d.rowsq = e_hh; d.colsq = cb_sumsq;
+    d.C = e_dist; d.ldc = 1024; d.mode = EPI_VQDIST; d.rowsq = e_hh; d.colsq = cb_sumsq; d.cus = cus;
     gemm_nt(d, st);
     argmin_dist_rows(e_dist, P, 1024, prompts, st);
     }
@@ -583,7 +589,7 @@ int gsv_engine::encode(const gsv_utt* u, float* x, int64_t* prompts, hipStream_t
         GemmArgs b{};
         b.M = L; b.N = 512; b.K = 1024;
         b.A = e_bert; b.lda = 1024; b.W = bert_w; b.ldw = 1024; b.w_f16 = 0;
-        b.C = e_bproj; b.ldc = 512; b.mode = EPI_STORE;
+        b.C = e_bproj; b.ldc = 512; b.mode = EPI_STORE; b.cus = cus;
         gemm_nt(b, st);
         bproj = e_bproj;
     }
@@ -603,12 +609,16 @@ int gsv_engine::prefill_slot(int b, const float* x, int L, const int64_t* pr, in
     audio_embed_prompts(pr, P, emb_audio, alpha_audio, pe_tab, pH + (size_t)L * 512, st);
     hipLaunchKernelGGL(k_fill_row_len, dim3((N0 + 255) / 256), dim3(256), 0, st, prow_len, L, N0);
     const long sstride = (long)16 * tmax * 32;
+    // the CUs this stream can use (the vocoder's for a prefetch, a lane's for a missed one): the
+    // small-M GEMM form follows them (gemm_nt); no result depends on it
+    const int cus = stream_cus(st);
     for (int l = 0; l < 24; ++l) {
         const T2SLayerW& W = layers[l];
         GemmArgs g{};
         g.M = N0; g.N = 1536; g.K = 512; g.A = pH; g.lda = 512;
         g.W = W.w_in; g.ldw = 512; g.w_f16 = 1; g.bias = W.b_in;
         g.C = pQ; g.ldc = 512; g.mode = EPI_QKV;
+        g.cus = cus; g.small_ns = gemm_small_ns;
         g.kv.k = kcache[l] + b * sstride; g.kv.v = vcache[l] + b * sstride;
         g.kv.tmax = tmax; g.kv.pos0 = 0; g.kv.seq_stride = sstride;
         gemm_nt(g, st);
@@ -624,6 +634,7 @@ int gsv_engine::prefill_slot(int b, const float* x, int L, const int64_t* pr, in
         GemmArgs go{};
         go.M = N0; go.N = 512; go.K = 512; go.A = pO; go.lda = 512;
         go.W = W.w_out; go.ldw = 512; go.w_f16 = 1; go.bias = W.b_out;
+        go.cus = cus; go.small_ns = gemm_small_ns;
         if (slabs) {
             go.C = pSlab; go.ldc = 512; go.mode = EPI_SLAB; go.ksplit = 4; go.slab_stride = slab_stride;
             gemm_nt(go, st);
@@ -637,10 +648,12 @@ int gsv_engine::prefill_slot(int b, const float* x, int L, const int64_t* pr, in
         g1.M = N0; g1.N = 2048; g1.K = 512; g1.A = pH1; g1.lda = 512;
         g1.W = W.w1; g1.ldw = 512; g1.w_f16 = 1; g1.bias = W.b1;
         g1.C = pF; g1.ldc = 2048; g1.mode = EPI_RELU;
+        g1.cus = cus; g1.small_ns = gemm_small_ns;
         gemm_nt(g1, st);
         GemmArgs g2{};
         g2.M = N0; g2.N = 512; g2.K = 2048; g2.A = pF; g2.lda = 2048;
         g2.W = W.w2; g2.ldw = 2048; g2.w_f16 = 1; g2.bias = W.b2;
+        g2.cus = cus; g2.small_ns = gemm_small_ns;
         if (slabs) {
             g2.C = pSlab; g2.ldc = 512; g2.mode = EPI_SLAB; g2.ksplit = 8; g2.slab_stride = slab_stride;
             gemm_nt(g2, st);
@@ -2067,6 +2080,11 @@ extern "C" int gsv_set_option(gsv_engine* eng, const char* name, int value) {
         eng->vits_lanes = value;
     } else if (n == "gemm_presplit") {   // the packed prefill's large GEMMs on pre-split A (same results)
         eng->use_presplit = value != 0;
+    } else if (n == "vits_slab_fuse") {   // the front's LayerNorms / gates read the convs' split-K slabs (same results)
+        eng->vits_slab_fuse = value != 0;
+    } else if (n == "gemm_small_ns") {   // ring depth of the small-M GEMM form: 0 = by grid and CUs, 2 / 3 / 4 forced
+        if (value != 0 && (value < 2 || value > 4)) return set_error(GSV_E_ARG, "gemm_small_ns: 0, 2, 3 or 4");
+        eng->gemm_small_ns = value;
     } else if (n == "convh_ws") {   // 0 off, 1 every batched generator pass, 2 (default) a batch vocoded alone
         eng->convh_ws = std::max(0, std::min(2, value));
     } else if (n == "vits_fork") {
@@ -2175,6 +2193,7 @@ extern "C" int gsv_get_counter(gsv_engine* eng, const char* name, int64_t* value
     if (n == "persist_timeouts") *value = eng->persist_timeouts;
     else if (n == "persist1_f16_reruns") *value = eng->persist1_f16_reruns;
     else if (n == "vits_f32_reruns") *value = eng->vits_f32_reruns;
+    else if (n == "vits_slab_consumers") *value = eng->vits_slab_consumers.load();
     else if (n == "vits_packed_fronts") *value = eng->vits_packed_fronts;
     else if (n == "sv_f32_reruns") *value = eng->sv_f32_reruns;
     else if (n == "w16_split_tensors") *value = eng->w16_split_tensors;

@@ -1,5 +1,6 @@
 // Internal engine state (not part of the C ABI).
 #pragma once
+#include <atomic>
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
@@ -265,6 +266,12 @@ struct gsv_engine {
     // fp16 hi / lo planes of pk_H, pk_H1, pk_F: the A operands of the pre-split large-M GEMMs
     __half *pk_Hh = nullptr, *pk_Hl = nullptr, *pk_H1h = nullptr, *pk_H1l = nullptr, *pk_Fh = nullptr, *pk_Fl = nullptr;
     bool use_presplit = true;          // option "gemm_presplit": the packed prefill's large GEMMs on pre-split A
+    std::atomic<long> vits_slab_consumers{0};   // counter "vits_slab_consumers": LayerNorm / gate launches that summed a
+                                       // conv's slabs themselves (lane threads issue fronts side by side)
+    bool vits_slab_fuse = true;        // option "vits_slab_fuse": the vocoder front's LayerNorms and WaveNet gates sum
+                                       // the split-K slabs of the conv before them (0: a reduce launch each; same results)
+    int gemm_small_ns = 0;             // option "gemm_small_ns": ring depth of the small-M GEMM form (0: by the
+                                       // grid and the CUs of its stream; 2 / 3 / 4 forced; same results)
     int *pk_rowinfo = nullptr, *pk_last = nullptr;
     int64_t* pk_prompts = nullptr;
     int* pk_tiles = nullptr;

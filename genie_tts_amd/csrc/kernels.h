@@ -61,6 +61,10 @@ struct GemmArgs {
     // (lda elements per row), as the kernels' own split of the f32 values would form them
     const __half* Ah; const __half* Al;
     __half* Ch; __half* Cl;          // EPI_RELU_SPLIT outputs (ldc elements per row)
+    // Host only (no kernel reads them, so no result depends on them): the CUs the launch's stream
+    // can use (0: not stated, as the whole chip), by which the small-M fp16-weight form picks its ring depth, and
+    // that depth forced (option "gemm_small_ns": 2 / 3 / 4; 0 = the rule of gemm_nt)
+    int cus, small_ns;
 };
 void gemm_nt(const GemmArgs& a, hipStream_t s);
 // Args of a GEMM with fp16 weights W[N][K] (ldw = K): C = epi(A W^T + bias)

@@ -456,9 +456,24 @@ __global__ __launch_bounds__(64 * (BM / 32) * (BN / 32 / WTN)) void k_gemm_x3(Ge
 //     and LDS waits.  On the packed prefill of 64 sentences (22,848 rows) it takes 0.67x
 //     k_gemm_x2's time, bit-identical; one-block-per-CU 128 x 128 forms were slower than
 //     k_gemm_x2 (profiles/r04e_gemm_big.txt).  With a.Ah set, its pre-split-A twin.
-//   SmallM: M <= 512 -- four stages; other tile shapes and ring depths were within 10 %
-//     (profiles/r03f_gemm_sweep.txt).
+//   SmallM: M <= 512 -- four stages (96 KB, one block per CU) while the grid fits the CUs of its
+//     stream in one round; other tile shapes and ring depths were within 10 % there
+//     (profiles/r03f_gemm_sweep.txt).  A larger grid -- a prefill on the 64 vocoder CUs or on a
+//     96-CU decode lane -- would run in rounds of a block that mostly waits for its DMA, so it
+//     takes two stages (48 KB, three blocks per CU): 0.59-0.61x the four-stage time on 64 CUs for
+//     q/k/v, FFN1 and FFN2 at 225 rows, 0.76x for the out-projection; three stages (72 KB, two
+//     blocks) lie between and are kept for option gemm_small_ns only; the XCD remap changed
+//     nothing (profiles/vstream_chain_gemm_forms.txt).  The ring depth changes neither the MFMA
+//     sequence nor the K partition (equal hashes there).
 enum class X3Form { SplitW, LargeM, SmallM };
+
+// Ring depth of the small-M form for `blocks` workgroups: two stages when the caller names the CUs
+// of its stream (a.cus) and the grid exceeds them, else four; a.small_ns forces it.
+static int small_m_stages(const GemmArgs& a, long blocks) {
+    if (a.small_ns) return a.small_ns;
+    return a.cus > 0 && blocks > a.cus ? 2 : 4;
+}
+
 static void launch_x3(const GemmArgs& a, int z, hipStream_t s, X3Form form) {
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3((a.N + 63) / 64, (a.M + 63) / 64, z), dim3(256), 0, s, a);
@@ -469,7 +484,16 @@ static void launch_x3(const GemmArgs& a, int z, hipStream_t s, X3Form form) {
             if (a.Ah) go(k_gemm_x3<64, 64, 2, false, 1, true, true>);
             else go(k_gemm_x3<64, 64, 2, false, 1, true>);
             break;
-        case X3Form::SmallM: go(k_gemm_x3<64, 64, 4>); break;
+        case X3Form::SmallM:
+            switch (small_m_stages(a, (long)((a.N + 63) / 64) * ((a.M + 63) / 64) * z)) {
+                case 2: go(k_gemm_x3<64, 64, 2>); break;
+                case 3: go(k_gemm_x3<64, 64, 3>); break;
+                case 4: go(k_gemm_x3<64, 64, 4>); break;
+                default:
+                    std::fprintf(stderr, "gemm_nt: small-M ring depth %d\n", a.small_ns);
+                    std::abort();
+            }
+            break;
     }
 }
 

@@ -72,6 +72,12 @@ struct ConvArgs {
     int ws;
 };
 void conv1d(const ConvArgs& a, hipStream_t s);
+// conv1d that leaves a split-K conv unreduced: returns the slab count (>= 2) it left in a.part,
+// [nsplit][Cout][n_t] with conv1d's own nsplit and no reduce launched -- the next launch on the
+// stream sums them (ln_channels_slabs, wn_gate_slabs; a.out, a.mode and a.bias are then the
+// consumer's business) -- or 0 when the conv finished a.out itself (unsplit, or taken by conv1d_h).
+// For convs with o_tstride 1, o_toff 0, o_len = n_t, one phase.
+int conv1d_deferred(const ConvArgs& a, hipStream_t s);
 // seg[t] for t < n: i with off[i] * f <= t < (off[i] + len[i]) * f, else -1 (off ascending)
 void seg_fill(int* seg, long n, const int* off, const int* len, int nseg, int f, hipStream_t s);
 // f16-split path; returns false (nothing launched) when the shape is not covered.
@@ -98,6 +104,10 @@ bool mrf_pair(const MrfPairArgs& a, hipStream_t s);
 void mean3(const float* a, const float* b, const float* c, float* out, long n, float div, hipStream_t s);
 void ln_channels(const float* x, const float* y, float* out, int C, int T, const float* g,
                  const float* b, hipStream_t s, const int* seg = nullptr);
+// ... with y = bias[c] + sum_z slab_z[c][t] (bias may be null), the slabs of conv1d_deferred summed in
+// slab order from slab 0: bit for bit the conv's reduce followed by ln_channels.  C % 16 == 0, C <= 256.
+void ln_channels_slabs(const float* x, const float* slabs, int nsplit, const float* bias, float* out, int C, int T,
+                       const float* g, const float* b, hipStream_t s, const int* seg = nullptr);
 
 // Multi-head attention with optional relative-position terms (window W).
 //   element (i, c) of q/k/v/out at ptr[i*ts + c*cs]; head h uses channels [h*dk, (h+1)*dk)
@@ -122,6 +132,10 @@ void mha(const MhaArgs& a, hipStream_t s);
 void codebook_upsample2(const int64_t* sem, int G, const float* cb, float* out, hipStream_t s);
 void embed_channels(const int64_t* ids, int n, const float* emb, int C, float* out, hipStream_t s);
 void wn_gate(const float* xin, float* acts, int H, int T, hipStream_t s);      // tanh(a)*sigmoid(b)
+// ... on the slabs [nsplit][2H][T] of a deferred CV_VEC conv: xin = (bias[co] + sum_z slab_z) + vec[co]
+// (vec + seg[t] * vec_sstride in a segmented batch, where a gap column gives 0)
+void wn_gate_slabs(const float* slabs, int nsplit, const float* bias, const float* vec, long vec_sstride,
+                   const int* seg, float* acts, int H, int T, hipStream_t s);
 void glu_resid(const float* h, const float* x, float* out, int C, int T, long x_cs, long x_ts,
                hipStream_t s);                                                  // out = x + a*sigmoid(b)
 void noise_zp(const float* m, const float* logs, const float* eps, float scale, float* z, int n,
@@ -212,7 +226,10 @@ struct VitsWorkspace {
     float* gx[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // resblocks 1 / 2 on side streams
     float *ge = nullptr, *pad = nullptr, *reim = nullptr, *spec = nullptr, *r0 = nullptr, *r1 = nullptr;
     float *r2 = nullptr, *r3 = nullptr, *rq = nullptr, *ratt = nullptr;
-    float* splitk = nullptr;   // conv split-K partial slabs
+    // conv split-K partial slabs.  A deferred conv (conv1d_deferred) leaves its slabs here until its
+    // consumer has run: the consumer is the next launch on the same stream, and no conv may be
+    // issued on this scratch between the two (the text branch on the side stream has splitk2).
+    float* splitk = nullptr;
     long splitk_cap = 0;
     float* splitk2 = nullptr;  // ... of the front's text branch on the side stream (same capacity)
     float *sv = nullptr, *pe_ge = nullptr;

@@ -189,8 +189,10 @@ static int conv_ci(int K) {
     }
 }
 
-void conv1d(const ConvArgs& a, hipStream_t s) {
-    if (a.wh && conv1d_h(a, s)) return;
+// defer: a conv that splits K leaves its slabs in a.part and launches no reduce.  Returns the
+// slab count (1: the conv wrote its own output).
+static int conv1d_run(const ConvArgs& a, hipStream_t s, bool defer) {
+    if (a.wh && conv1d_h(a, s)) return 1;
     dim3 grid((a.n_t + CONV_BN - 1) / CONV_BN, (a.Cout + CONV_BM - 1) / CONV_BM,
               a.phases > 0 ? a.phases : 1);
     // Under-filled grids (the T=2G / S-frame encoder, MRTE and flow convs) split
@@ -211,12 +213,20 @@ void conv1d(const ConvArgs& a, hipStream_t s) {
         case 5: launch_conv<5>(a, grid, s); break;
         case 7: launch_conv<7>(a, grid, s); break;
         case 11: launch_conv<11>(a, grid, s); break;
-        default: return;   // host validates K
+        default: return 1;   // host validates K
     }
-    if (nsplit > 1) {
+    if (nsplit > 1 && !defer) {
         const long n = (long)a.Cout * a.n_t;
         hipLaunchKernelGGL(k_conv_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, nsplit);
     }
+    return nsplit;
+}
+
+void conv1d(const ConvArgs& a, hipStream_t s) { conv1d_run(a, s, false); }
+
+int conv1d_deferred(const ConvArgs& a, hipStream_t s) {
+    const int nsplit = conv1d_run(a, s, true);
+    return nsplit > 1 ? nsplit : 0;
 }
 
 __global__ __launch_bounds__(256) void k_mean3(const float4* __restrict__ a, const float4* __restrict__ b,
@@ -313,30 +323,14 @@ __global__ __launch_bounds__(256) void k_ln_channels(const float* x, const float
     }
 }
 
-// Narrow form for C <= 256, C % 16 == 0 (the 192-channel encoders): one wave per
-// 4 time columns, lane = (t & 3) + 4 * channel group; reductions by shuffles over
-// the 16 groups, so short sequences still spread over T/4 waves.
-__global__ __launch_bounds__(64) void k_ln_channels_w(const float* x, const float* y, float* out,
-                                                     int C, int T, const float* g, const float* b,
-                                                     const int* seg) {
-    const int lane = threadIdx.x, tl = lane & 3, cg = lane >> 2;
-    const int t = blockIdx.x * 4 + tl;
-    const bool ok = t < T;
-    const bool gap = ok && seg && seg[t] < 0;
+// The statistics and the output of the narrow form from a lane's 16 channel values
+// (v[i]: channel cg + 16 i of column t; 0 past C).  The lane writes channels i = i0, i0 + di, ...
+__device__ __forceinline__ void ln_w_finish(const float (&v)[16], float* out, int C, int T, const float* g,
+                                            const float* b, int t, int cg, bool ok, bool gap, int i0, int di) {
     const int nc = C >> 4;
-    float v[16];
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        float xv = 0.f;
-        if (i < nc && ok) {
-            const long o = (long)(cg + 16 * i) * T + t;
-            xv = x[o];
-            if (y) xv = xv + y[o];
-        }
-        v[i] = xv;
-        s += xv;
-    }
+    for (int i = 0; i < 16; ++i) s += v[i];
 #pragma unroll
     for (int o = 4; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
     const float mean = s / (float)C;
@@ -353,10 +347,91 @@ __global__ __launch_bounds__(64) void k_ln_channels_w(const float* x, const floa
     if (!ok) return;
 #pragma unroll
     for (int i = 0; i < 16; ++i)
-        if (i < nc) {
+        if (i < nc && i % di == i0) {
             const int c = cg + 16 * i;
             out[(long)c * T + t] = gap ? 0.f : (v[i] - mean) / den * g[c] + b[c];
         }
+}
+
+// Narrow form for C <= 256, C % 16 == 0 (the 192-channel encoders): one wave per
+// 4 time columns, lane = (t & 3) + 4 * channel group; reductions by shuffles over
+// the 16 groups, so short sequences still spread over T/4 waves.
+__global__ __launch_bounds__(64) void k_ln_channels_w(const float* x, const float* y, float* out,
+                                                     int C, int T, const float* g, const float* b,
+                                                     const int* seg) {
+    const int lane = threadIdx.x, tl = lane & 3, cg = lane >> 2;
+    const int t = blockIdx.x * 4 + tl;
+    const bool ok = t < T;
+    const bool gap = ok && seg && seg[t] < 0;
+    const int nc = C >> 4;
+    float v[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        float xv = 0.f;
+        if (i < nc && ok) {
+            const long o = (long)(cg + 16 * i) * T + t;
+            xv = x[o];
+            if (y) xv = xv + y[o];
+        }
+        v[i] = xv;
+    }
+    ln_w_finish(v, out, C, T, g, b, t, cg, ok, gap, 0, 1);
+}
+
+// The narrow form on a split-K conv's slabs [nsplit][C][T] (conv1d_deferred): out = LN(x + y),
+// y = bias[c] + sum_z slab_z in k_conv_reduce's and conv_epilogue's order.  Four waves share the 4
+// columns of a block: wave w sums the slabs of channels cg + 16 i, i = w, w + 4, ..., so 4 T / 4
+// waves have the slab loads in flight; then every wave forms the statistics from all values (the
+// one-wave form's arithmetic) and writes its own channels.
+__global__ __launch_bounds__(256) void k_ln_channels_ws(const float* x, const float* slabs, int nsplit,
+                                                        const float* bias, float* out, int C, int T,
+                                                        const float* g, const float* b, const int* seg) {
+    __shared__ float vs[16][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, tl = lane & 3, cg = lane >> 2;
+    const int t = blockIdx.x * 4 + tl;
+    const bool ok = t < T;
+    const bool gap = ok && seg && seg[t] < 0;
+    const int nc = C >> 4;
+    const long n = (long)C * T;
+    float xa[4], ya[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = w + 4 * k;
+        xa[k] = ya[k] = 0.f;
+        if (i < nc && ok) xa[k] = x[(long)(cg + 16 * i) * T + t];
+    }
+    // the four channels' slabs 8 at a time: 32 loads in flight per lane, each sum in slab order
+    for (int s0 = 0; s0 < nsplit; s0 += 8) {
+        float p[4][8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = w + 4 * k;
+            const long o = (long)(cg + 16 * i) * T + t;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                p[k][j] = (i < nc && ok && s0 + j < nsplit) ? slabs[(long)(s0 + j) * n + o] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (s0 + j < nsplit) ya[k] = (s0 + j == 0) ? p[k][j] : ya[k] + p[k][j];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = w + 4 * k;
+        float xv = 0.f;
+        if (i < nc && ok) {
+            const float y = bias ? bias[cg + 16 * i] + ya[k] : ya[k];
+            xv = xa[k] + y;
+        }
+        vs[i][lane] = xv;
+    }
+    __syncthreads();
+    float v[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = vs[i][lane];
+    ln_w_finish(v, out, C, T, g, b, t, cg, ok, gap, w, 4);
 }
 
 void ln_channels(const float* x, const float* y, float* out, int C, int T, const float* g,
@@ -367,6 +442,13 @@ void ln_channels(const float* x, const float* y, float* out, int C, int T, const
         hipLaunchKernelGGL(k_ln_channels, dim3((T + 63) / 64), dim3(256), 0, s, x, y, out, C, T, g, b);
     else
         std::abort();   // the segmented front's LayerNorms are all 192-channel
+}
+
+void ln_channels_slabs(const float* x, const float* slabs, int nsplit, const float* bias, float* out, int C, int T,
+                       const float* g, const float* b, hipStream_t s, const int* seg) {
+    if (C % 16 != 0 || C > 256 || nsplit < 2) std::abort();   // the narrow form's channel counts only
+    hipLaunchKernelGGL(k_ln_channels_ws, dim3((T + 3) / 4), dim3(256), 0, s, x, slabs, nsplit, bias, out, C, T, g,
+                       b, seg);
 }
 
 // ----------------------------------------------------------------- attention
@@ -511,6 +593,50 @@ __global__ void k_wn_gate(const float* xin, float* acts, int H, int T) {
 void wn_gate(const float* xin, float* acts, int H, int T, hipStream_t s) {
     const long n = (long)H * T;
     hipLaunchKernelGGL(k_wn_gate, dim3((n + 255) / 256), dim3(256), 0, s, xin, acts, H, T);
+}
+// ... on the slabs [nsplit][2H][T] of a split-K CV_VEC conv (conv1d_deferred): a / b = (bias[co] +
+// sum_z slab_z) + vec[co] in k_conv_reduce's and conv_epilogue's order; a gap column gives 0, as
+// the gate of the zeros the conv writes there
+__global__ __launch_bounds__(256) void k_wn_gate_slabs(const float* slabs, int nsplit, const float* bias,
+                                                       const float* vec, long vec_sstride, const int* seg,
+                                                       float* acts, int H, int T) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const long hn = (long)H * T;
+    if (i >= hn) return;
+    const int co = (int)(i / T), t = (int)(i - (long)co * T);
+    if (seg) {
+        const int sg = seg[t];
+        if (sg < 0) {
+            acts[i] = 0.f;
+            return;
+        }
+        vec += (long)sg * vec_sstride;
+    }
+    // both halves' slabs 8 at a time (16 loads in flight), each sum in slab order
+    float sa = 0.f, sb = 0.f;
+    for (int s0 = 0; s0 < nsplit; s0 += 8) {
+        float pa[8], pb[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            pa[j] = s0 + j < nsplit ? slabs[(long)(s0 + j) * 2 * hn + i] : 0.f;
+            pb[j] = s0 + j < nsplit ? slabs[(long)(s0 + j) * 2 * hn + hn + i] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (s0 + j < nsplit) {
+                sa = (s0 + j == 0) ? pa[j] : sa + pa[j];
+                sb = (s0 + j == 0) ? pb[j] : sb + pb[j];
+            }
+    }
+    const float va = bias ? bias[co] + sa : sa, vb = bias ? bias[co + H] + sb : sb;
+    const float a = va + vec[co], b = vb + vec[co + H];
+    acts[i] = tanhf(a) * (1.0f / (1.0f + expf(-b)));
+}
+void wn_gate_slabs(const float* slabs, int nsplit, const float* bias, const float* vec, long vec_sstride,
+                   const int* seg, float* acts, int H, int T, hipStream_t s) {
+    const long n = (long)H * T;
+    hipLaunchKernelGGL(k_wn_gate_slabs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, slabs, nsplit, bias, vec,
+                       vec_sstride, seg, acts, H, T);
 }
 
 // Conv1dGLU: out = x + a * sigmoid(b), h = [a; b] channel-major [2C][T]

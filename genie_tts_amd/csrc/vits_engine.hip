@@ -369,6 +369,17 @@ static ConvArgs cargs(const Conv& c, const float* x, int T, float* out, int mode
 static void attn_encoder(gsv_engine* e, const std::vector<AttnLayer>& Ls, float* x, int T, float* qkv,
                          float* att, float* tmp, float* ffn, hipStream_t s, const int* seg = nullptr,
                          const int* rows = nullptr) {
+    // x = LN(x + conv(in)): a split-K conv leaves its slabs to the LayerNorm (vits_slab_fuse), which
+    // sums them as the conv's reduce would; an unsplit one goes through tmp
+    auto conv_ln = [&](const Conv& c, const float* in, const float* g, const float* b) {
+        const ConvArgs a = cargs(c, in, T, tmp, CV_STORE, seg);
+        int ns = 0;
+        if (e->vits_slab_fuse) ns = conv1d_deferred(a, s);
+        else conv1d(a, s);
+        if (ns) ++e->vits_slab_consumers;
+        if (ns) ln_channels_slabs(x, a.part, ns, a.bias, x, 192, T, g, b, s, seg);
+        else ln_channels(x, tmp, x, 192, T, g, b, s, seg);
+    };
     for (const AttnLayer& L : Ls) {
         conv1d(cargs(L.qkv, x, T, qkv, CV_STORE, seg), s);
         MhaArgs m{};
@@ -380,11 +391,9 @@ static void attn_encoder(gsv_engine* e, const std::vector<AttnLayer>& Ls, float*
         m.ek = L.ek; m.ev = L.ev; m.window = 4;
         m.row_seg = rows;
         mha(m, s);
-        conv1d(cargs(L.o, att, T, tmp, CV_STORE, seg), s);
-        ln_channels(x, tmp, x, 192, T, L.g1, L.b1, s, seg);
+        conv_ln(L.o, att, L.g1, L.b1);
         conv1d(cargs(L.ffn1, x, T, ffn, CV_RELU, seg), s);
-        conv1d(cargs(L.ffn2, ffn, T, tmp, CV_STORE, seg), s);
-        ln_channels(x, tmp, x, 192, T, L.g2, L.b2, s, seg);
+        conv_ln(L.ffn2, ffn, L.g2, L.b2);
     }
 }
 
@@ -1122,8 +1131,13 @@ int gsv_engine::vits_front(VitsWorkspace& W, const int64_t* text_seq, int n_text
             ConvArgs ci = cargs(fl.in_l[l], W.fh, T, W.fx, CV_VEC, sT);
             ci.vec = gcond + l * 384;
             ci.vec_sstride = fl.cond.cout;
-            conv1d(ci, s);
-            wn_gate(W.fx, W.fa, 192, T, s);
+            // a split-K in_layer leaves its slabs to the gate (vits_slab_fuse)
+            int ns = 0;
+            if (vits_slab_fuse) ns = conv1d_deferred(ci, s);
+            else conv1d(ci, s);
+            if (ns) ++vits_slab_consumers;
+            if (ns) wn_gate_slabs(ci.part, ns, ci.bias, ci.vec, ci.vec_sstride, ci.seg, W.fa, 192, T, s);
+            else wn_gate(W.fx, W.fa, 192, T, s);
             if (l < 3) {
                 ConvArgs rs = cargs(fl.rs[l], W.fa, T, W.fh, CV_SPLIT_RESID, sT);
                 rs.res = W.fh; rs.split = 192; rs.out2 = W.fskip; rs.res2 = W.fskip;

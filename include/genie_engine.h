@@ -444,6 +444,12 @@ int gsv_request_stop(gsv_engine* eng, int32_t on);
  * "convh_ws" (the 7- / 11-tap MRF convs with 64 / 128 input channels weight-stationary, k_conv_ws:
  * 2 -- the default -- in a synchronous gsv_vits_decode_batch, whose vocoder has the GPU to
  * itself; 1 in every batched generator pass; 0 off; bit-identical),
+ * "gemm_small_ns" (ring depth of the small-M fp16-weight GEMM form: 0, the default, follows the
+ * launch's grid and the CUs of its stream -- a prefill on the vocoder CUs takes a shallower
+ * ring, so two or three blocks share a CU; 2 / 3 / 4 forced; bit-identical),
+ * "vits_slab_fuse" (1, default: the vocoder front's LayerNorms after an attention out-projection
+ * or FFN2 and its WaveNet gates sum the split-K slabs of the conv before them; 0: that conv
+ * launches its own reduce; bit-identical),
  * A/B options measured and left off: "vocoder_first" (a batched decode waits for the running
  * vocoder batch), "lanes_all_cus" (under vocoder_cus, the batch lanes on every CU),
  * "knob0".."knob3" (decode tuning variants),
@@ -460,7 +466,8 @@ int gsv_set_option(gsv_engine* eng, const char* name, int value);
  * configured), "lane_launches_0" / "lane_launches_1" (persistent launches issued on each
  * lane; the synchronous paths count on lane 0), "persist1_f16_reruns" (fp16-range fallbacks),
  * "vits_f32_reruns", "vits_packed_fronts" (vocoder batches whose text/flow part ran
- * packed), "sv_f32_reruns", "w16_split_tensors" (fp32 weights kept as hi + lo
+ * packed), "vits_slab_consumers" (LayerNorm / gate launches of the vocoder front that summed
+ * the split-K slabs of the conv before them, option "vits_slab_fuse"), "sv_f32_reruns", "w16_split_tensors" (fp32 weights kept as hi + lo
  * planes), "stops" (generates abandoned by gsv_request_stop), "graph_fallbacks"
  * (per-step decode loops run eagerly because their hipGraph capture failed -- e.g.
  * invalidated by another thread's device-wide synchronisation), "retired_bytes" (device

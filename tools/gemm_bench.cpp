@@ -2,6 +2,11 @@
 // T2S prefill (N0 = 225 rows), batched decode (B = 64), RoBERTa (40 tokens), CN-HuBERT
 // (300 frames), the packed prefill of 64 sentences (22848 rows).  Prints per-shape microseconds (hipEvents over 200 launches), the max
 // error against a double-precision host GEMM on sampled entries, and a bit hash of C.
+// Usage: gemm_bench [--cus N] [--forms]
+//   --cus N: launch on a stream masked to CUs [0, N) and tell gemm_nt so (GemmArgs::cus)
+//   --forms: the small-M shapes (M <= 512, no split weights) only, each in every ring depth of the
+//            small-M form (GemmArgs::small_ns 4, 3, 2, and 0 = the rule); the hashes of one shape
+//            must be equal across the forms
 // Build: hipcc -O3 --offload-arch=gfx950 tools/gemm_bench.cpp -Igenie_tts_amd/csrc
 //        -Lgenie_tts_amd/_lib -lgenie_engine -Wl,-rpath,$PWD/genie_tts_amd/_lib -o tools/gemm_bench
 #include <hip/hip_runtime.h>
@@ -24,7 +29,26 @@ static float frand() {
 }
 static int irand(int n) { return (int)(frand() * n) % n; }
 
-int main() {
+int main(int argc, char** argv) {
+    int cus = 0;
+    bool forms = false;
+    for (int i = 1; i < argc; ++i) {
+        if (!strcmp(argv[i], "--cus") && i + 1 < argc) cus = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--forms")) forms = true;
+    }
+    hipStream_t st = 0;
+    if (cus > 0) {
+        int ncu = 0;
+        (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0);
+        if (cus > ncu) cus = ncu;
+        std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
+        for (int i = 0; i < cus; ++i) mask[i / 32] |= 1u << (i % 32);
+        if (hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
+            fprintf(stderr, "CU-masked stream failed\n");
+            return 1;
+        }
+        printf("# stream masked to %d of %d CUs\n", cus, ncu);
+    }
     const Shape shapes[] = {
         {"prefill qkv     ", 225, 1536, 512, gsv::EPI_STORE, 1},
         {"prefill out slab", 225, 512, 512, gsv::EPI_SLAB, 4},
@@ -52,6 +76,7 @@ int main() {
     };
     for (const Shape& sh : shapes) {
         const int M = sh.M, N = sh.N, K = sh.K;
+        if (forms && (M > 512 || sh.sw || sh.ps)) continue;
         // seed per shape (not per position in the list): a PS / W16 row draws the same A, W, bias
         // as the plain row of the same shape, so their hashes are comparable
         rng_state = 7ull + 1000003ull * M + 8191ull * N + 131ull * K + 17ull * sh.mode + sh.ksplit;
@@ -95,18 +120,25 @@ int main() {
             (void)hipMemcpy(dAl, al.data(), A.size() * 2, hipMemcpyHostToDevice);
             g.Ah = dAh; g.Al = dAl;
         }
-        gsv::gemm_nt(g, 0);
+        g.cus = cus;
+        const int form_list[] = {4, 3, 2, 0};
+        for (int fi = 0; fi < (forms ? 4 : 1); ++fi) {
+        g.small_ns = forms ? form_list[fi] : 0;
+        (void)hipMemsetAsync(dC, 0xff, cElems * 4, st);
+        gsv::gemm_nt(g, st);
         (void)hipDeviceSynchronize();
         hipEvent_t e0, e1;
         (void)hipEventCreate(&e0);
         (void)hipEventCreate(&e1);
         const int iters = M > 4096 ? 20 : 200;
-        (void)hipEventRecord(e0, 0);
-        for (int i = 0; i < iters; ++i) gsv::gemm_nt(g, 0);
-        (void)hipEventRecord(e1, 0);
+        (void)hipEventRecord(e0, st);
+        for (int i = 0; i < iters; ++i) gsv::gemm_nt(g, st);
+        (void)hipEventRecord(e1, st);
         (void)hipEventSynchronize(e1);
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, e0, e1);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
         std::vector<float> C(cElems);
         (void)hipMemcpy(C.data(), dC, cElems * 4, hipMemcpyDeviceToHost);
         // sampled check against a double-precision host GEMM
@@ -138,8 +170,10 @@ int main() {
         }
         const double wbytes = (double)N * K * 2, abytes = (double)M * K * 4;
         const double us = ms * 1000.0 / iters;
+        if (forms) printf("ns=%2d ", g.small_ns);
         printf("%s M=%5d N=%5d K=%5d split=%2d: %8.2f us  (%6.0f GB/s of W+A)  maxerr %.2e  hash %016llx\n", sh.name,
                M, N, K, sh.ksplit, us, (wbytes + abytes) / (us * 1e3), maxerr, hsh);
+        }
         (void)hipFree(dA); (void)hipFree(dW); (void)hipFree(dB); (void)hipFree(dC);
         if (dWl) (void)hipFree(dWl);
         if (dAh) { (void)hipFree(dAh); (void)hipFree(dAl); }
