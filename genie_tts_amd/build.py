@@ -59,13 +59,14 @@ def build(verbose: bool = False, force: bool = False) -> str:
     cc = _hipcc()
 
     def src_mtime(src):
-        # a .hip that includes another .hip (t2s_persist1m.hip) is stale when the included one changes
+        # a .hip that includes another .hip (t2s_persist1m.hip) is stale when the included one
+        # (or one that it includes in turn: t2s_persistm_each.hip) changes
         t = os.path.getmtime(src)
         with open(src) as f:
             for line in f:
                 m = re.match(r'\s*#include\s+"([^"]+\.hip)"', line)
                 if m:
-                    t = max(t, os.path.getmtime(os.path.join(CSRC, m.group(1))))
+                    t = max(t, src_mtime(os.path.join(CSRC, m.group(1))))
         return t
 
     def compile_one(src):

@@ -484,6 +484,7 @@ int gsv_engine::reserve(int batch, int tokens) {
     stopf = (uint8_t*)A(nb);
     seen = (uint32_t*)A((size_t)nb * 33 * 4);
     forceb = (int*)A(nb * 4);
+    seq_tab = (SeqSampler*)A((size_t)nb * sizeof(SeqSampler));
     dslab = (float*)A((size_t)8 * nb * 2048 * 4);   // batched-decode split-K slabs (2 regions)
     h = (float*)A((size_t)nb * 512 * 4);
     h1 = (float*)A((size_t)nb * 512 * 4);
@@ -506,7 +507,7 @@ int gsv_engine::reserve(int batch, int tokens) {
     prompts_buf = (int64_t*)A((size_t)nt * 8);
     acc64 = (long long*)A((size_t)nb * ACC_SEQ * 8);
     pSlab = (float*)A((size_t)8 * nt * 512 * 4);
-    if (!pF || !prompts_buf || !acc64 || !pSlab) return set_error(GSV_E_HIP, "state allocation failed");
+    if (!pF || !prompts_buf || !acc64 || !pSlab || !seq_tab) return set_error(GSV_E_HIP, "state allocation failed");
     // stream-ordered (no null-stream call while another thread may be capturing), then waited
     // for: id lives on this frame
     hipMemsetAsync(acc64, 0, (size_t)nb * ACC_SEQ * 8, stream);
@@ -601,7 +602,8 @@ int gsv_engine::encode(const gsv_utt* u, float* x, int64_t* prompts, hipStream_t
 
 // ------------------------------------------------------------ prefill
 int gsv_engine::prefill_slot(int b, const float* x, int L, const int64_t* pr, int P,
-                             const gsv_sampler* sp, float* logits_out, hipStream_t st, int noise_b) {
+                             const gsv_sampler* sp, float* logits_out, hipStream_t st, int noise_b,
+                             const SeqSampler* per) {
     const int N0 = L + P;
     if (N0 + 1 > tmax) return set_error(GSV_E_CAPACITY, "prefill exceeds reserved tokens");
     if (x != pH) hipMemcpyAsync(pH, x, (size_t)L * 512 * 4, hipMemcpyDeviceToDevice, st);
@@ -669,13 +671,14 @@ int gsv_engine::prefill_slot(int b, const float* x, int L, const int64_t* pr, in
     lg.B = 1; lg.N = 1025; lg.K = 512; lg.src = pH + (size_t)(N0 - 1) * 512; lg.lds = 512;
     lg.W = w_pred; lg.C = logits + (size_t)b * 1025; lg.ldc = 1025; lg.mode = EPI_STORE;
     gemv_f16(lg, st);
-    SampleArgs sa = sampler_args(sp, 1);
+    SampleArgs sa = sampler_args(sp, 1, per);
     sa.logits = logits + (size_t)b * 1025;
     sa.y = y + (size_t)b * tmax; sa.ny = ny + b; sa.seen = seen + (size_t)b * 33;
     sa.done = done + b; sa.stop_out = nullptr; sa.steps = steps + b; sa.kvlen = kvlen + b;
     sa.prefill = 1; sa.logits_out = logits_out; sa.ldlo = 1025;
     sa.b0 = noise_b >= 0 ? noise_b : b;   // Philox counter: the slot's own noise for its first-stage token
-                                          // (a prefetch into slot 1 draws slot 0's: it is decoded there)
+                                          // (a prefetch into slot 1 draws slot 0's: it is decoded there);
+                                          // with a table, its entry: per[b0]
     sample_tokens(sa, st);
     return hipGetLastError() == hipSuccess ? 0 : set_error(GSV_E_HIP, "prefill launch");
 }
@@ -736,7 +739,8 @@ int gsv_engine::ensure_packed(int rows, int B) {
     return 0;
 }
 
-int gsv_engine::prefill_packed(int B, const gsv_utt* utts, const gsv_sampler* sp, hipStream_t st) {
+int gsv_engine::prefill_packed(int B, const gsv_utt* utts, const gsv_sampler* sp, hipStream_t st,
+                               const SeqSampler* per) {
     std::vector<int> off(B + 1, 0), Ls(B), Ps(B), poff(B + 1, 0);
     for (int b = 0; b < B; ++b) {
         Ls[b] = utts[b].n_ref + utts[b].n_text;
@@ -873,13 +877,13 @@ int gsv_engine::prefill_packed(int B, const gsv_utt* utts, const gsv_sampler* sp
     lg.M = B; lg.N = 1025; lg.K = 512; lg.A = pk_xlast; lg.lda = 512; lg.W = w_pred; lg.ldw = 512;
     lg.w_f16 = 1; lg.C = logits; lg.ldc = 1025; lg.mode = EPI_STORE;
     gemm_nt(lg, st);
-    SampleArgs sa = sampler_args(sp, B);
+    SampleArgs sa = sampler_args(sp, B, per);
     sa.prefill = 1;
     sample_tokens(sa, st);
     return hipGetLastError() == hipSuccess ? 0 : set_error(GSV_E_HIP, "packed prefill launch");
 }
 
-SampleArgs gsv_engine::sampler_args(const gsv_sampler* sp, int B) {
+SampleArgs gsv_engine::sampler_args(const gsv_sampler* sp, int B, const SeqSampler* per) {
     SampleArgs sa{};
     sa.B = B;
     sa.logits = logits; sa.ldl = 1025;
@@ -897,11 +901,13 @@ SampleArgs gsv_engine::sampler_args(const gsv_sampler* sp, int B) {
     sa.prefill = 0;
     sa.stop_req = stop_word;
     sa.stop_hit = stop_word + 1;
+    sa.per = per;
     return sa;
 }
 
 // ------------------------------------------------------------ decode step
-void gsv_engine::decode_step(int B, const gsv_sampler* sp, float* logits_out, hipStream_t st) {
+void gsv_engine::decode_step(int B, const gsv_sampler* sp, float* logits_out, hipStream_t st,
+                             const SeqSampler* per) {
     const long sstride = (long)16 * tmax * 32;
     // fixed-point hand-off slices of layer l (fused path): FFN output, attention output
     const bool acc = use_acc && B <= 8 && tmax <= 1024;
@@ -996,14 +1002,22 @@ void gsv_engine::decode_step(int B, const gsv_sampler* sp, float* logits_out, hi
         lg.w_f16 = 1; lg.C = logits; lg.ldc = 1025; lg.mode = EPI_STORE;
         gemm_nt(lg, st);
     }
-    SampleArgs sa = sampler_args(sp, B);
+    SampleArgs sa = sampler_args(sp, B, per);
     sa.logits_out = logits_out; sa.ldlo = 1025;
     if (acc) { sa.acc_zero = acc64; sa.acc_n = ACC_SEQ; }
     sample_tokens(sa, st);
 }
 
-hipGraphExec_t gsv_engine::step_graph(int B, const gsv_sampler* sp, int chunk, hipStream_t st) {
-    const std::string key = std::to_string(B) + ":" + std::to_string(chunk) + ":" +
+hipGraphExec_t gsv_engine::step_graph(int B, const gsv_sampler* sp, int chunk, hipStream_t st,
+                                      const SeqSampler* per) {
+    // A table launch's graph is keyed by the table's address instead of the sampler values: the
+    // sampler kernel reads the table when it runs, so the graph replays correctly after the
+    // table's contents change, and it is never shared with a launch-wide graph ("T:").  The
+    // address moves only in reserve(), which drops every graph.
+    const std::string key = per ? "T:" + std::to_string(B) + ":" + std::to_string(chunk) + ":" +
+                                      std::to_string(sp->max_steps) + ":" + std::to_string(sp->force_steps) + ":" +
+                                      std::to_string((uintptr_t)per)
+                                : std::to_string(B) + ":" + std::to_string(chunk) + ":" +
                             std::to_string(sp->top_k) + ":" + std::to_string(sp->greedy) + ":" +
                             std::to_string(sp->seed) + ":" + std::to_string(sp->max_steps) + ":" +
                             std::to_string(sp->force_steps) + ":" +
@@ -1018,7 +1032,7 @@ hipGraphExec_t gsv_engine::step_graph(int B, const gsv_sampler* sp, int chunk, h
         (void)hipGetLastError();
         return nullptr;
     }
-    for (int i = 0; i < chunk; ++i) decode_step(B, sp, nullptr, st);
+    for (int i = 0; i < chunk; ++i) decode_step(B, sp, nullptr, st, per);
     if ((graph_err = hipStreamEndCapture(st, &g)) != hipSuccess) {
         if (g) hipGraphDestroy(g);
         // an invalidated capture can leave the stream in capture mode: end it, or every later
@@ -1042,17 +1056,18 @@ hipGraphExec_t gsv_engine::step_graph(int B, const gsv_sampler* sp, int chunk, h
     return ex;
 }
 
-int gsv_engine::decode_loop(int B, const gsv_sampler* sp, hipStream_t st, bool allow_persist) {
+int gsv_engine::decode_loop(int B, const gsv_sampler* sp, hipStream_t st, bool allow_persist,
+                            const SeqSampler* per) {
     // Steps are launched as replayed hipGraphs (chunk of 8 steps, tail by 1-step
     // graphs so forced lengths run no extra step).  The host polls the done flags
     // of chunk k while chunk k+1 already runs, so the GPU never waits on the host.
     const int limit = loop_limit > 0 ? loop_limit : sp->force_steps > 0 ? sp->force_steps : sp->max_steps;
     if (stop_requested()) return stopped_error();
-    if (allow_persist && use_persist && persist_family(B) && persist_admit()) return decode_persistent(B, sp, st);
+    if (allow_persist && use_persist && persist_family(B) && persist_admit()) return decode_persistent(B, sp, st, per);
     __atomic_store_n(stop_word + 1, 0, __ATOMIC_RELEASE);   // no kernel of this engine runs: the loops are synchronous
     const int chunk = 8;
-    hipGraphExec_t ex8 = step_graph(B, sp, chunk, st);
-    hipGraphExec_t ex1 = ex8 ? step_graph(B, sp, 1, st) : nullptr;
+    hipGraphExec_t ex8 = step_graph(B, sp, chunk, st, per);
+    hipGraphExec_t ex1 = ex8 ? step_graph(B, sp, 1, st, per) : nullptr;
     // A capture that fails (another host thread's device-wide synchronisation -- hipFree,
     // hipDeviceSynchronize -- can invalidate it) leaves this loop on eager launches of the
     // same kernels: same results, more launch overhead; the next loop tries to capture again.
@@ -1064,7 +1079,7 @@ int gsv_engine::decode_loop(int B, const gsv_sampler* sp, hipStream_t st, bool a
     }
     auto run_steps = [&](hipGraphExec_t ex, int n) -> int {
         if (eager) {
-            for (int i = 0; i < n; ++i) decode_step(B, sp, nullptr, st);
+            for (int i = 0; i < n; ++i) decode_step(B, sp, nullptr, st, per);
             const hipError_t le = hipGetLastError();
             return le == hipSuccess ? 0 : hip_error("decode step launch", le);
         }
@@ -1089,7 +1104,7 @@ int gsv_engine::decode_loop(int B, const gsv_sampler* sp, hipStream_t st, bool a
         if (probe_pending && launched == chunk) {
             n = 1;
             probe_now = true;
-            decode_step(B, sp, nullptr, st);
+            decode_step(B, sp, nullptr, st, per);
             probe_now = false;
             probe_pending = false;
             probed = true;
@@ -1141,8 +1156,8 @@ bool gsv_engine::persist_family(int B) const {
            (B == 1 || (use_persist1m && B <= std::min(PERSIST1M_MAX_B, persist1m_max_batch())));
 }
 
-int gsv_engine::decode_persistent(int B, const gsv_sampler* sp, hipStream_t st) {
-    return decode_persistent_as(B, sp, st);
+int gsv_engine::decode_persistent(int B, const gsv_sampler* sp, hipStream_t st, const SeqSampler* per) {
+    return decode_persistent_as(B, sp, st, per);
 }
 
 // Enqueue one persistent decode launch on st (no host wait): the error word is
@@ -1151,7 +1166,8 @@ int gsv_engine::decode_persistent(int B, const gsv_sampler* sp, hipStream_t st) 
 // on the vocoder CUs right after the kernel.  one: the single-sequence kernel
 // (t2s_persist1.hip) instead of the general one.
 int gsv_engine::persist_enqueue(int B, const gsv_sampler* sp, hipStream_t st, int* perr_dst,
-                                hipEvent_t k0, hipEvent_t k1, char* res_dst, int res_b, int lane) {
+                                hipEvent_t k0, hipEvent_t k1, char* res_dst, int res_b, int lane,
+                                const SeqSampler* per) {
     // lane 1 (a started single-utterance generate beside the one on the engine stream): its own
     // ring, epoch, error word and slot; the kernel sees "sequence 0" at the slot's addresses
     if (lane != 0 && (B != 1 || st != lane1.st || max_batch <= LaneBook::slot_of(lane)))
@@ -1214,6 +1230,7 @@ int gsv_engine::persist_enqueue(int B, const gsv_sampler* sp, hipStream_t st, in
     a.greedy = sp->greedy; a.seed = sp->seed; a.max_steps = sp->max_steps; a.force_steps = sp->force_steps;
     a.top_p = norm_top_p(sp->top_p);
     a.force_b = forceb + slot;
+    a.per = per;
     a.ring = (unsigned long long*)pws;
     a.epoch = pepoch;
     a.err = perr;
@@ -1233,9 +1250,9 @@ int gsv_engine::persist_enqueue(int B, const gsv_sampler* sp, hipStream_t st, in
     const int pm_groups = std::min({persistm_max_groups(), decode_cus() / persistm_grid(1), B});
     const bool pm = B > 1 && use_persistm && B >= persistm_min_b && pm_groups >= persistm_groups(B);
     if (pm) a.groups = pm_groups;
-    const hipError_t le = B == 1 ? decode_persist1(a, st, k0, k1)
-                          : pm   ? decode_persistm(a, st, k0, k1)
-                                 : decode_persist1m(a, st, k0, k1);
+    const hipError_t le = B == 1 ? (per ? decode_persist1_each : decode_persist1)(a, st, k0, k1)
+                          : pm   ? (per ? decode_persistm_each : decode_persistm)(a, st, k0, k1)
+                                 : (per ? decode_persist1m_each : decode_persist1m)(a, st, k0, k1);
     if (le != hipSuccess)
         return set_error(GSV_E_HIP, "persistent decode launch");
     ++persist_launches;
@@ -1312,12 +1329,12 @@ int gsv_engine::stopped_error() {
     return set_error(GSV_E_STOPPED, "stopped by gsv_request_stop");
 }
 
-int gsv_engine::decode_persistent_as(int B, const gsv_sampler* sp, hipStream_t st) {
+int gsv_engine::decode_persistent_as(int B, const gsv_sampler* sp, hipStream_t st, const SeqSampler* per) {
     if (!perr_host && hipHostMalloc((void**)&perr_host, 64, hipHostMallocDefault) != hipSuccess)
         return set_error(GSV_E_HIP, "pinned alloc");
     const bool probe = timing && kev[0] != nullptr;
     if (int r = persist_enqueue(B, sp, st, perr_host, probe ? kev[0] : nullptr, probe ? kev[1] : nullptr,
-                                res_batch ? res_pin : nullptr, res_batch))
+                                res_batch ? res_pin : nullptr, res_batch, 0, per))
         return r;
     if (const hipError_t we = host_wait(st)) return hip_error("persistent decode sync", we);
     // code 3 (or any code under a pending stop): a stop request abandoned the launch
@@ -1328,7 +1345,7 @@ int gsv_engine::decode_persistent_as(int B, const gsv_sampler* sp, hipStream_t s
     // per-step graphs (t2s_decode.hip: f32 activations on the VALU, no fp16 operand).
     if (*perr_host == 2) {
         ++persist1_f16_reruns;
-        return decode_loop(B, sp, st, false);
+        return decode_loop(B, sp, st, false, per);
     }
     // code 1: a hand-off waited past its bound -- the launch's workgroups were not
     // all resident (other work on the device) or stalled.  Every workgroup left
@@ -1336,7 +1353,7 @@ int gsv_engine::decode_persistent_as(int B, const gsv_sampler* sp, hipStream_t s
     // per-step graphs, which need no co-residency.
     if (*perr_host == 1) {
         note_persist_timeout();
-        return decode_loop(B, sp, st, false);
+        return decode_loop(B, sp, st, false, per);
     }
     if (*perr_host != 0)
         return set_error(GSV_E_HIP, "persistent decode failed (code " + std::to_string(*perr_host) + ")");
@@ -1701,30 +1718,29 @@ extern "C" int gsv_t2s_read_kv(gsv_engine* eng, int seq, int layer, float* k, fl
     return hipStreamSynchronize(st) == hipSuccess ? 0 : set_error(GSV_E_HIP, "read_kv");
 }
 
-extern "C" int gsv_t2s_generate(gsv_engine* eng, int batch, const gsv_utt* utts,
-                                const gsv_sampler* s, int64_t* out_tokens, int32_t out_stride,
-                                int32_t* out_len, void* stream) {
-    ENG_CHECK(eng);
-    hipSetDevice(eng->device);
-    if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
-    if (batch <= 0 || !utts || !out_tokens || !out_len) return set_error(GSV_E_ARG, "bad args");
-    gsv_sampler sp;
-    if (int e = norm_sampler(s, sp)) return e;
+// The body of gsv_t2s_generate (each == null: sp is the one sampler) and gsv_t2s_generate_each
+// (each: batch normalised samplers of one max_steps; sp then holds the launch-wide values:
+// max_steps, force_steps 0 -- an entry's folds into its sequence's force_b -- and the greedy
+// mode).  Every sampler site of the generate reads the same device table.
+static int generate_run(gsv_engine* eng, int batch, const gsv_utt* utts, const gsv_sampler& sp,
+                        const gsv_sampler* each, const int32_t* streams, int64_t* out_tokens,
+                        int32_t out_stride, int32_t* out_len, void* stream) {
     if (eng->stop_requested()) return eng->stopped_error();   // Inference.py:96-97 at step 0
     if (int e = eng->gen_drain()) return e;   // started generates finish first (results stay queued)
     // prefetched (gsv_t2s_prefetch, launched into slot 1 during the last decode)?  A
     // queued prefetch is for a later call: it stays queued (launched during this
     // decode) unless this is a batch, whose prefill uses slot 1 itself.
-    const bool hit = batch == 1 && eng->pf_pending && same_utt(utts[0], eng->pf_p.u) &&
+    const bool hit = !each && batch == 1 && eng->pf_pending && same_utt(utts[0], eng->pf_p.u) &&
                      same_sampler(sp, eng->pf_p.sp);
     if (!hit)
         if (int e = eng->pf_drop(batch == 1)) return e;
-    const int steps_cap = sp.force_steps > 0 ? sp.force_steps : sp.max_steps;
     int need = 0, limit = 0;
     std::vector<int> hforce(batch);
     for (int b = 0; b < batch; ++b) {
         if (utts[b].force_steps < 0) return set_error(GSV_E_ARG, "negative force_steps");
-        hforce[b] = utts[b].force_steps;
+        // the utterance's own forced length wins; a table entry's folds in here
+        hforce[b] = utts[b].force_steps > 0 ? utts[b].force_steps : each ? std::max(0, each[b].force_steps) : 0;
+        const int steps_cap = sp.force_steps > 0 ? sp.force_steps : sp.max_steps;
         const int cap_b = hforce[b] > 0 ? hforce[b] : steps_cap;
         const int n0 = utts[b].n_ref + utts[b].n_text + utts[b].n_ssl / 2;
         need = std::max(need, n0 + cap_b + 16);
@@ -1734,6 +1750,15 @@ extern "C" int gsv_t2s_generate(gsv_engine* eng, int batch, const gsv_utt* utts,
     StreamScope sc(eng, stream);
     hipStream_t st = sc.st();
     if (!hit) hipMemcpyAsync(eng->forceb, hforce.data(), batch * 4, hipMemcpyHostToDevice, st);
+    const SeqSampler* per = nullptr;
+    if (each) {   // the table: one copy, ahead of the prefill's sampler (reserve() sized it)
+        eng->seq_tab_host.resize(batch);
+        for (int b = 0; b < batch; ++b)
+            eng->seq_tab_host[b] = SeqSampler{each[b].top_k, each[b].temperature, each[b].repetition_penalty,
+                                              each[b].top_p, each[b].greedy, streams ? streams[b] : b, each[b].seed};
+        hipMemcpyAsync(eng->seq_tab, eng->seq_tab_host.data(), batch * sizeof(SeqSampler), hipMemcpyHostToDevice, st);
+        per = eng->seq_tab;
+    }
     eng->loop_limit = limit;
     if (hit) {   // encoded and prefilled ahead (gsv_t2s_prefetch): slot 1 -> slot 0
         eng->pf_take(st, hforce[0]);
@@ -1741,14 +1766,14 @@ extern "C" int gsv_t2s_generate(gsv_engine* eng, int batch, const gsv_utt* utts,
     if (eng->timing) hipEventRecord(eng->ev[0], st);
     hipMemsetAsync(eng->done, 1, eng->max_batch, st);
     if (batch > 1 && eng->use_packed) {
-        if (int e = eng->prefill_packed(batch, utts, &sp, st)) return e;
+        if (int e = eng->prefill_packed(batch, utts, &sp, st, per)) return e;
     } else {
         for (int b = 0; b < batch; ++b) {
             const gsv_utt& u = utts[b];
             const int L = u.n_ref + u.n_text, P = u.n_ssl / 2;
             if (int e = eng->encode(&u, eng->pH, eng->prompts_buf, st)) return e;
             if (eng->timing && b == 0) hipEventRecord(eng->ev[1], st);
-            if (int e = eng->prefill_slot(b, eng->pH, L, eng->prompts_buf, P, &sp, nullptr, st)) return e;
+            if (int e = eng->prefill_slot(b, eng->pH, L, eng->prompts_buf, P, &sp, nullptr, st, -1, per)) return e;
         }
     }
     }
@@ -1759,7 +1784,7 @@ extern "C" int gsv_t2s_generate(gsv_engine* eng, int batch, const gsv_utt* utts,
     // option vocoder_first: the decode waits for the overlapped vocoder batch, so none of that
     // batch's kernels is left pending while the persistent decode holds every CU
     if (eng->vocoder_first && eng->vb_active) eng->vits_batch_order(st);
-    const int rc = eng->decode_loop(batch, &sp, st);
+    const int rc = eng->decode_loop(batch, &sp, st, true, per);
     eng->res_batch = 0;
     eng->perr_zeroed = false;
     eng->loop_limit = 0;
@@ -1778,6 +1803,54 @@ extern "C" int gsv_t2s_generate(gsv_engine* eng, int batch, const gsv_utt* utts,
         hipEventElapsedTime(&eng->ms[2], eng->ev[2], eng->ev[3]);
     }
     return eng->trim_results(eng->res_pin, batch, out_tokens, out_stride, out_len);
+}
+
+extern "C" int gsv_t2s_generate(gsv_engine* eng, int batch, const gsv_utt* utts,
+                                const gsv_sampler* s, int64_t* out_tokens, int32_t out_stride,
+                                int32_t* out_len, void* stream) {
+    ENG_CHECK(eng);
+    hipSetDevice(eng->device);
+    if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
+    if (batch <= 0 || !utts || !out_tokens || !out_len) return set_error(GSV_E_ARG, "bad args");
+    gsv_sampler sp;
+    if (int e = norm_sampler(s, sp)) return e;
+    return generate_run(eng, batch, utts, sp, nullptr, nullptr, out_tokens, out_stride, out_len, stream);
+}
+
+// Normalise and check a per-sequence sampler list (gsv_t2s_generate_each, gsv_debug_sample_each):
+// every entry as norm_sampler checks one (the message names the entry), streams >= 0.
+static int norm_each(int batch, const gsv_sampler* samplers, const int32_t* streams, std::vector<gsv_sampler>& out) {
+    out.resize(batch);
+    for (int b = 0; b < batch; ++b) {
+        if (int e = norm_sampler(&samplers[b], out[b]))
+            return set_error(e, "samplers[" + std::to_string(b) + "]: " + gsv_last_error());
+        if (streams && streams[b] < 0) return set_error(GSV_E_ARG, "streams[" + std::to_string(b) + "] is negative");
+    }
+    return 0;
+}
+
+extern "C" int gsv_t2s_generate_each(gsv_engine* eng, int batch, const gsv_utt* utts,
+                                     const gsv_sampler* samplers, const int32_t* streams,
+                                     int64_t* out_tokens, int32_t out_stride, int32_t* out_len, void* stream) {
+    ENG_CHECK(eng);
+    hipSetDevice(eng->device);
+    if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
+    if (batch <= 0 || !utts || !samplers || !out_tokens || !out_len) return set_error(GSV_E_ARG, "bad args");
+    std::vector<gsv_sampler> each;
+    if (int e = norm_each(batch, samplers, streams, each)) return e;
+    // launch-wide: max_steps (one for all), the greedy mode -- the fused-argmax step end, which
+    // reads the launch-wide rep_penalty / temperature, only when every entry is greedy with the
+    // same two values; otherwise the sampler path, a greedy entry on sample_block's greedy branch
+    gsv_sampler sp = each[0];
+    sp.force_steps = 0;
+    for (int b = 1; b < batch; ++b) {
+        if (each[b].max_steps != sp.max_steps)
+            return set_error(GSV_E_ARG, "samplers[" + std::to_string(b) + "]: max_steps differs from samplers[0] (it is launch-wide)");
+        if (!each[b].greedy || each[b].repetition_penalty != sp.repetition_penalty ||
+            each[b].temperature != sp.temperature)
+            sp.greedy = 0;
+    }
+    return generate_run(eng, batch, utts, sp, each.data(), streams, out_tokens, out_stride, out_len, stream);
 }
 
 // ============================================================ asynchronous generate
@@ -2007,14 +2080,15 @@ extern "C" int gsv_get_timing(gsv_engine* eng, float* ms4) {
     return 0;
 }
 
-extern "C" int gsv_debug_sample(const float* logits, const uint32_t* seen, int B, const gsv_sampler* s,
-                                int step, int64_t* tokens, uint8_t* stop, void* stream) {
-    if (!logits || !seen || !s || !tokens || B <= 0 || step < 1) return set_error(GSV_E_ARG, "bad args");
-    if (int e = check_sampler(s)) return e;
+// One k_sample launch over B rows on a scratch decode state; tab: a host table of B entries
+// (copied into the scratch), or null for the launch-wide sampler s.
+static int debug_sample_run(const float* logits, const uint32_t* seen, int B, const gsv_sampler* s,
+                            const SeqSampler* tab, int step, int64_t* tokens, uint8_t* stop, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    // scratch decode state: y[b] (ldy 1), ny = 0, steps = step - 1, done = 0
+    // scratch decode state: y[b] (ldy 1), ny = 0, steps = step - 1, done = 0 (+ the table)
     char* buf = nullptr;
-    const size_t need = (size_t)B * (8 + 4 + 4 + 4 + 1 + 132);
+    const size_t state = ((size_t)B * (8 + 4 + 4 + 4 + 1 + 132) + 31) & ~(size_t)31;
+    const size_t need = state + (tab ? (size_t)B * sizeof(SeqSampler) : 0);
     if (hipMalloc(&buf, need) != hipSuccess) return set_error(GSV_E_HIP, "scratch");
     int64_t* y = (int64_t*)buf;
     int* ny = (int*)(y + B);
@@ -2032,11 +2106,36 @@ extern "C" int gsv_debug_sample(const float* logits, const uint32_t* seen, int B
     a.top_k = s->top_k; a.temperature = s->temperature; a.rep_penalty = s->repetition_penalty;
     a.top_p = norm_top_p(s->top_p);
     a.greedy = s->greedy; a.seed = s->seed; a.max_steps = 1 << 30; a.force_steps = 0; a.prefill = 0;
+    if (tab) {
+        SeqSampler* dtab = (SeqSampler*)(buf + state);
+        hipMemcpyAsync(dtab, tab, (size_t)B * sizeof(SeqSampler), hipMemcpyHostToDevice, st);
+        a.per = dtab;
+    }
     sample_tokens(a, st);
     hipMemcpyAsync(tokens, y, (size_t)B * 8, hipMemcpyDeviceToDevice, st);
     const bool ok = hipStreamSynchronize(st) == hipSuccess;
     hipFree(buf);
     return ok ? 0 : set_error(GSV_E_HIP, "debug sample");
+}
+
+extern "C" int gsv_debug_sample(const float* logits, const uint32_t* seen, int B, const gsv_sampler* s,
+                                int step, int64_t* tokens, uint8_t* stop, void* stream) {
+    if (!logits || !seen || !s || !tokens || B <= 0 || step < 1) return set_error(GSV_E_ARG, "bad args");
+    if (int e = check_sampler(s)) return e;
+    return debug_sample_run(logits, seen, B, s, nullptr, step, tokens, stop, stream);
+}
+
+extern "C" int gsv_debug_sample_each(const float* logits, const uint32_t* seen, int B, const gsv_sampler* samplers,
+                                     const int32_t* streams, int step, int64_t* tokens, uint8_t* stop,
+                                     void* stream) {
+    if (!logits || !seen || !samplers || !tokens || B <= 0 || step < 1) return set_error(GSV_E_ARG, "bad args");
+    std::vector<gsv_sampler> each;
+    if (int e = norm_each(B, samplers, streams, each)) return e;
+    std::vector<SeqSampler> tab(B);
+    for (int b = 0; b < B; ++b)
+        tab[b] = SeqSampler{each[b].top_k, each[b].temperature, each[b].repetition_penalty, each[b].top_p,
+                            each[b].greedy, streams ? streams[b] : b, each[b].seed};
+    return debug_sample_run(logits, seen, B, &each[0], tab.data(), step, tokens, stop, stream);
 }
 
 extern "C" int gsv_set_option(gsv_engine* eng, const char* name, int value) {

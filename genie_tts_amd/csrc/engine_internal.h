@@ -131,6 +131,8 @@ struct gsv_engine {
     uint32_t* seen = nullptr;
     float* dslab = nullptr;           // batched decode: [2][4][B][2048] split-K slabs
     int* forceb = nullptr;            // per-slot forced loop length (gsv_utt.force_steps; 0 = sampler rule)
+    gsv::SeqSampler* seq_tab = nullptr;   // [max_batch] per-sequence samplers of gsv_t2s_generate_each (reserve())
+    std::vector<gsv::SeqSampler> seq_tab_host;   // its host image (the source of the generate's one copy)
     int loop_limit = 0;               // >0: loop-step bound of the current generate (max over its slots)
     float *h = nullptr, *h1 = nullptr, *s1 = nullptr, *s2 = nullptr, *q = nullptr, *o = nullptr;
     float *f = nullptr, *logits = nullptr;
@@ -278,13 +280,19 @@ struct gsv_engine {
     int pk_tile_cap = 0;
     std::vector<int> pk_host;
     int ensure_packed(int rows, int B);
-    int prefill_packed(int B, const gsv_utt* utts, const gsv_sampler* sp, hipStream_t st);
+    // per (everywhere below): the per-sequence sampler table of gsv_t2s_generate_each (seq_tab), or
+    // null; with a table sp holds the launch-wide values (max_steps, the greedy mode, force_steps 0)
+    int prefill_packed(int B, const gsv_utt* utts, const gsv_sampler* sp, hipStream_t st,
+                       const gsv::SeqSampler* per = nullptr);
     int prefill_slot(int b, const float* x, int L, const int64_t* pr, int P, const gsv_sampler* sp,
-                     float* logits_out, hipStream_t st, int noise_b = -1);
-    gsv::SampleArgs sampler_args(const gsv_sampler* sp, int B);
-    void decode_step(int B, const gsv_sampler* sp, float* logits_out, hipStream_t st);
-    hipGraphExec_t step_graph(int B, const gsv_sampler* sp, int chunk, hipStream_t st);
-    int decode_loop(int B, const gsv_sampler* sp, hipStream_t st, bool allow_persist = true);
+                     float* logits_out, hipStream_t st, int noise_b = -1, const gsv::SeqSampler* per = nullptr);
+    gsv::SampleArgs sampler_args(const gsv_sampler* sp, int B, const gsv::SeqSampler* per = nullptr);
+    void decode_step(int B, const gsv_sampler* sp, float* logits_out, hipStream_t st,
+                     const gsv::SeqSampler* per = nullptr);
+    hipGraphExec_t step_graph(int B, const gsv_sampler* sp, int chunk, hipStream_t st,
+                              const gsv::SeqSampler* per = nullptr);
+    int decode_loop(int B, const gsv_sampler* sp, hipStream_t st, bool allow_persist = true,
+                    const gsv::SeqSampler* per = nullptr);
     long persist_timeouts = 0;         // persistent launches that timed out (co-running work) and re-ran as graphs
     int persist_timeout_run = 0;       // consecutive ones (2: a back-off hold on the graphs begins)
     // back-off after repeated timeouts: the next persist_hold generates (or until persist_hold_end,
@@ -309,8 +317,8 @@ struct gsv_engine {
     // workgroup waiting out one step of a 64-sequence decode, ~1.6 ms)
     static constexpr unsigned long long PERSIST_SPIN_TICKS = 20000000ull;
     unsigned long long persist_spin_ticks = PERSIST_SPIN_TICKS;   // option "persist_spin_ticks" (test hook)
-    int decode_persistent(int B, const gsv_sampler* sp, hipStream_t st);
-    int decode_persistent_as(int B, const gsv_sampler* sp, hipStream_t st);
+    int decode_persistent(int B, const gsv_sampler* sp, hipStream_t st, const gsv::SeqSampler* per = nullptr);
+    int decode_persistent_as(int B, const gsv_sampler* sp, hipStream_t st, const gsv::SeqSampler* per = nullptr);
     bool persist_family(int B) const;
     // generate's results (ny, steps, y rows) -> pinned host memory, enqueued by the
     // persistent decode before its own sync (one host round trip per generate)
@@ -322,7 +330,8 @@ struct gsv_engine {
     void enqueue_results(int batch, hipStream_t st, char* dst, int slot = 0);
     int trim_results(const char* res, int batch, int64_t* out_tokens, int out_stride, int32_t* out_len);
     int persist_enqueue(int B, const gsv_sampler* sp, hipStream_t st, int* perr_dst, hipEvent_t k0,
-                        hipEvent_t k1, char* res_dst, int res_b, int lane = 0);
+                        hipEvent_t k1, char* res_dst, int res_b, int lane = 0,
+                        const gsv::SeqSampler* per = nullptr);
     void probe_sample(hipEvent_t k0, hipEvent_t k1);
     // asynchronous single-utterance generate (gsv_t2s_generate_start / _finish): up to
     // two in flight on the engine stream, so the next decode is queued behind the

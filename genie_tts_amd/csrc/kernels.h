@@ -209,6 +209,16 @@ void decode_embed(int B, const int64_t* y, long ldy, const int* ny, const __half
                   const float* alpha, const float* pe, float* h, const uint8_t* done,
                   hipStream_t s);
 
+// One sequence's sampler in a batched decode (gsv_t2s_generate_each): a device table of B
+// entries, read by the sampler site of sequence b when SampleArgs::per / PersistArgs::per is
+// set.  `stream` is the Philox counter word a launch without a table fills with the batch
+// slot.  b is uniform over the block, so an entry is one uniform 32-byte read; the table is
+// constant for the length of a launch.
+struct SeqSampler {
+    int top_k; float temperature, rep_penalty, top_p; int greedy; int stream; uint64_t seed;
+};
+static_assert(sizeof(SeqSampler) == 32, "SeqSampler: 32 bytes");
+
 struct SampleArgs {
     int B;
     const float* logits; long ldl;     // [B][1025]
@@ -231,6 +241,8 @@ struct SampleArgs {
     const int* stop_req;               // host-mapped stop word (gsv_request_stop): set -> the sequence finishes
     int* stop_hit;                     // host-mapped, or null: set to 1 when the stop word ended a sequence, so the
                                        // host reports STOPPED even if the word is cleared before it looks
+    const SeqSampler* per;             // null: the launch-wide fields above, Philox stream b0 + b; else block b
+                                       // samples with per[b0 + b] (all seven values)
 };
 void sample_tokens(const SampleArgs& a, hipStream_t s);
 
@@ -277,6 +289,12 @@ struct PersistArgs {
                                                   // + b_in | W1 n1w | W1 n1b + b1] (1536, 1536, 2048, 2048 floats;
                                                   // layer 0: 0 | b_in), so a GEMV can run beside its LayerNorm stats;
                                                   // then [W_pred n2w_23 | W_pred n2b_23] (1025 each, the logits)
+    const SeqSampler* per;                        // null: the launch-wide sampler fields, Philox stream = slot b;
+                                                  // else sequence b samples with per[b].  `greedy` stays the
+                                                  // launch-wide mode (fused step end): the host sets it only when
+                                                  // every entry is greedy with one rep_penalty and temperature;
+                                                  // otherwise a greedy entry takes sample_block's greedy branch.
+                                                  // (Last: the kernarg offsets of the fields above are as before.)
 };
 constexpr int PERSIST_TMAX = 4096;   // longest key range of the persistent decode (its PE table)
 // Single-sequence persistent decode (t2s_persist1.hip): a.groups (3..8) layer
@@ -298,5 +316,11 @@ int persistm_groups(int B);      // the fewest groups that hold B sequences
 int persistm_max_groups();
 int persistm_grid(int groups);
 hipError_t decode_persistm(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop);
+// The three kernels built with the sampler site reading PersistArgs::per (a.per non-null; the
+// launchers above take a.per null only).  Translation units of their own (t2s_persist*_each.hip),
+// so the kernels of a launch without a table are the code they are without the read.
+hipError_t decode_persist1_each(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop);
+hipError_t decode_persist1m_each(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop);
+hipError_t decode_persistm_each(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop);
 
 }  // namespace gsv

@@ -218,6 +218,16 @@ struct SampleLds {
     float thr;
 };
 
+// The sampler of sequence b: the launch-wide fields with Philox stream `slot`, or entry b of
+// the table (a uniform read: b is uniform over the block).
+// TABLE is a compile-time choice: the persistent kernels exist in two builds (kernels.h),
+// and the one a launch without a table runs holds no trace of the read.
+template <bool TABLE, typename Args>
+__device__ __forceinline__ SeqSampler seq_sampler(const Args& a, int b, int slot) {
+    if (TABLE) return a.per[b];
+    return SeqSampler{a.top_k, a.temperature, a.rep_penalty, a.top_p, a.greedy, slot, a.seed};
+}
+
 // One sequence's sampling decision on NT threads (the whole block participates).
 // ld(i) returns logit i (i < VOCAB); seen_s is the presence bitmap (33 words, LDS);
 // step is the 1-based loop step fed to Philox (0 for the first stage).  Returns the

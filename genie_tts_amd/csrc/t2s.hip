@@ -1575,8 +1575,9 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
     __syncthreads();
     const int step = a.prefill ? 0 : step_s + 1;
     int raw = 0;
-    const int tok = sample_block<NT>([&](int i) { return lg[i]; }, seen_s, a.b0 + b, step, a.top_k, a.temperature,
-                                     a.rep_penalty, a.top_p, a.greedy, a.seed, a.ablate,
+    const SeqSampler q = a.per ? seq_sampler<true>(a, a.b0 + b, 0) : seq_sampler<false>(a, 0, a.b0 + b);
+    const int tok = sample_block<NT>([&](int i) { return lg[i]; }, seen_s, q.stream, step, q.top_k, q.temperature,
+                                     q.rep_penalty, q.top_p, q.greedy, q.seed, a.ablate,
                                      a.logits_out ? a.logits_out + (long)b * a.ldlo : nullptr, &raw, sh, srt);
     if (tid == 0) {
         if (a.ablate == 3) { a.y[(long)b * a.ldy + st_ny] = raw; a.ny[b] = st_ny + 1; return; }

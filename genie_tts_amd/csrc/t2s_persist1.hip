@@ -54,6 +54,18 @@
 
 namespace gsv {
 
+// PERSIST_SEQ_TABLE (t2s_persist1_each.hip, t2s_persist1m_each.hip, t2s_persistm_each.hip): the
+// same kernels with the sampler site reading PersistArgs::per, under the names *_each, in
+// translation units of their own -- as for PERSIST1_MULTI, so that the kernels a launch
+// without a table runs keep the code and the register allocation they have without the read.
+#ifdef PERSIST_SEQ_TABLE
+#define PERSIST_NAME(x) x##_each
+constexpr bool SEQ_TABLE = true;
+#else
+#define PERSIST_NAME(x) x
+constexpr bool SEQ_TABLE = false;
+#endif
+
 namespace {
 using namespace pk;
 constexpr int PT = 512;            // threads per workgroup (8 waves)
@@ -969,8 +981,9 @@ __device__ void run_attn(const PersistArgs& a, const Ws1& ws, Shared1& sh, int g
                 for (int i = tid; i < 1025; i += PT) sh.at.lg[i] = wait_gran(lgg + i, tag, a.err, ok, a.spin_ticks);
                 if (!block_ok1(ok, sh)) return;
                 STAMP1(1);
-                tok = sample_block<PT>([&](int i) { return sh.at.lg[i]; }, sh.seen, 0, st + 1, a.top_k,
-                                       a.temperature, a.rep_penalty, a.top_p, a.greedy, a.seed, 0, nullptr, &raw,
+                const SeqSampler q = seq_sampler<SEQ_TABLE>(a, 0, 0);
+                tok = sample_block<PT>([&](int i) { return sh.at.lg[i]; }, sh.seen, q.stream, st + 1, q.top_k,
+                                       q.temperature, q.rep_penalty, q.top_p, q.greedy, q.seed, 0, nullptr, &raw,
                                        sh.samp, topp_space(sh));
             }
             if (tid == 0) {
@@ -1674,8 +1687,9 @@ __device__ void run_attn_m(const PersistArgs& a, const WsSeq& base, Shared1& sh,
                 const int st = sh.m.st0[b] + s;
                 uint32_t* seen = sh.m.seens[b >> 4];
                 int raw = 0;
-                const int tok = sample_block<PT>([&](int i) { return sh.at.lg[i]; }, seen, b, st + 1, a.top_k,
-                                                 a.temperature, a.rep_penalty, a.top_p, a.greedy, a.seed, 0, nullptr,
+                const SeqSampler q = seq_sampler<SEQ_TABLE>(a, b, b);
+                const int tok = sample_block<PT>([&](int i) { return sh.at.lg[i]; }, seen, q.stream, st + 1, q.top_k,
+                                                 q.temperature, q.rep_penalty, q.top_p, q.greedy, q.seed, 0, nullptr,
                                                  &raw, sh.samp, topp_space(sh));
                 if (tid == 0) {
                     const int stop = (raw == 1024 || tok == 1024) ? 1 : 0;
@@ -1985,7 +1999,7 @@ __device__ void run_ffn_m(const PersistArgs& a, const WsSeq& base, Shared1& sh, 
 }
 
 #ifndef PERSIST1_NO_ENTRY   // (t2s_persistm.hip reuses the helpers above, not this kernel)
-__global__ __launch_bounds__(PT) void k_decode_persist1m(PersistArgs a) {
+__global__ __launch_bounds__(PT) void PERSIST_NAME(k_decode_persist1m)(PersistArgs a) {
     __shared__ Shared1 sh;
     WsSeq ws;
     ws.ring = a.ring;
@@ -2005,7 +2019,7 @@ __global__ __launch_bounds__(PT) void k_decode_persist1m(PersistArgs a) {
 
 #else   // the single-sequence kernel
 
-__global__ __launch_bounds__(PT) void k_decode_persist1(PersistArgs a) {
+__global__ __launch_bounds__(PT) void PERSIST_NAME(k_decode_persist1)(PersistArgs a) {
     __shared__ Shared1 sh;
     const Ws1 ws{a.ring, a.epoch, __builtin_amdgcn_make_buffer_rsrc(a.ring, 0, 0x7fffffff, 0x00020000)};
     const int grp = blockIdx.x / GW, r = blockIdx.x - grp * GW;
@@ -2018,23 +2032,29 @@ __global__ __launch_bounds__(PT) void k_decode_persist1(PersistArgs a) {
 
 #if defined(PERSIST1_MULTI) && defined(PERSIST1_NO_ENTRY)
 #elif defined(PERSIST1_MULTI)
+#ifndef PERSIST_SEQ_TABLE
 int persist1m_max_batch() { return MB; }
 size_t persist1m_ring_bytes(int B) { return (size_t)wsm_slot(B) * RING1 * 8; }
+#endif
 
-hipError_t decode_persist1m(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+hipError_t PERSIST_NAME(decode_persist1m)(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
     if (a.groups < 3 || a.groups > NG_MAX || a.B < 2 || a.B > MB) return hipErrorInvalidValue;
-    hipExtLaunchKernelGGL(k_decode_persist1m, dim3(a.groups * GW), dim3(PT), 0, s, start, stop, 0, a);
+    if (SEQ_TABLE != (a.per != nullptr)) return hipErrorInvalidValue;
+    hipExtLaunchKernelGGL(PERSIST_NAME(k_decode_persist1m), dim3(a.groups * GW), dim3(PT), 0, s, start, stop, 0, a);
     return hipGetLastError();
 }
 
 #else
+#ifndef PERSIST_SEQ_TABLE
 int persist1_grid(int groups) { return groups * GW; }
 int persist1_max_groups() { return NG_MAX; }
 
 size_t persist1_ring_bytes() { return (size_t)Ws1::SLOT * RING1 * 8; }
-hipError_t decode_persist1(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+#endif
+hipError_t PERSIST_NAME(decode_persist1)(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
     if (a.groups < 3 || a.groups > NG_MAX) return hipErrorInvalidValue;   // groups 1, 2 own the logits, sampler
-    hipExtLaunchKernelGGL(k_decode_persist1, dim3(a.groups * GW), dim3(PT), 0, s, start, stop, 0, a);
+    if (SEQ_TABLE != (a.per != nullptr)) return hipErrorInvalidValue;
+    hipExtLaunchKernelGGL(PERSIST_NAME(k_decode_persist1), dim3(a.groups * GW), dim3(PT), 0, s, start, stop, 0, a);
     return hipGetLastError();
 }
 

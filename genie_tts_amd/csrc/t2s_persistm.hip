@@ -1142,8 +1142,9 @@ __device__ void run_group(const PersistArgs& a, const WsSeq& base, SharedM& sh, 
             const int st = sh.st0[i] + s;
             uint32_t* seen = sh.seenq[i];
             int raw = 0;
-            const int tok = sample_block<PT>([&](int k) { return sh.at.lg[k]; }, seen, b, st + 1, a.top_k,
-                                             a.temperature, a.rep_penalty, a.top_p, a.greedy, a.seed, 0, nullptr, &raw,
+            const SeqSampler q = seq_sampler<SEQ_TABLE>(a, b, b);
+            const int tok = sample_block<PT>([&](int k) { return sh.at.lg[k]; }, seen, q.stream, st + 1, q.top_k,
+                                             q.temperature, q.rep_penalty, q.top_p, q.greedy, q.seed, 0, nullptr, &raw,
                                              sh.samp, reinterpret_cast<unsigned long long*>(sh.at.srt));
             if (tid == 0) {
                 const int stop = (raw == 1024 || tok == 1024) ? 1 : 0;
@@ -1192,7 +1193,7 @@ __device__ void run_group(const PersistArgs& a, const WsSeq& base, SharedM& sh, 
     }
 }
 
-__global__ __launch_bounds__(PT) void k_decode_persistm(PersistArgs a) {
+__global__ __launch_bounds__(PT) void PERSIST_NAME(k_decode_persistm)(PersistArgs a) {
     __shared__ alignas(16) SharedM sh;
     static_assert(offsetof(SharedM, at.srt) % 8 == 0 && sizeof(SharedM::at.srt) == TOPP_N * 8, "top_p sort space");
     WsSeq ws;
@@ -1211,13 +1212,16 @@ __global__ __launch_bounds__(PT) void k_decode_persistm(PersistArgs a) {
 
 }  // namespace
 
+#ifndef PERSIST_SEQ_TABLE
 int persistm_groups(int B) { return (B + MG - 1) / MG; }
 int persistm_max_groups() { return NSG_MAX; }
 int persistm_grid(int groups) { return groups * GWM; }
+#endif
 
-hipError_t decode_persistm(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+hipError_t PERSIST_NAME(decode_persistm)(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
     if (a.groups < 1 || a.groups > NSG_MAX || a.B < 1 || a.B > MB || a.B > MG * a.groups) return hipErrorInvalidValue;
-    hipExtLaunchKernelGGL(k_decode_persistm, dim3(a.groups * GWM), dim3(PT), 0, s, start, stop, 0, a);
+    if (SEQ_TABLE != (a.per != nullptr)) return hipErrorInvalidValue;
+    hipExtLaunchKernelGGL(PERSIST_NAME(k_decode_persistm), dim3(a.groups * GWM), dim3(PT), 0, s, start, stop, 0, a);
     return hipGetLastError();
 }
 

@@ -197,6 +197,10 @@ def lib():
                                          ctypes.c_float, vp, vp]
         L.gsv_debug_ktrace.argtypes = [vp, vp, ctypes.c_int]
         L.gsv_debug_sample.argtypes = [vp, vp, ctypes.c_int, ctypes.POINTER(Sampler), ctypes.c_int, vp, vp, vp]
+        L.gsv_t2s_generate_each.argtypes = [vp, ctypes.c_int, ctypes.POINTER(Utt), ctypes.POINTER(Sampler),
+                                            ctypes.POINTER(ctypes.c_int32), vp, i32, vp, vp]
+        L.gsv_debug_sample_each.argtypes = [vp, vp, ctypes.c_int, ctypes.POINTER(Sampler),
+                                            ctypes.POINTER(ctypes.c_int32), ctypes.c_int, vp, vp, vp]
         L.gsv_probe.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                 ctypes.POINTER(ctypes.c_float), vp]
         L.gsv_set_timing.argtypes = [vp, ctypes.c_int]
@@ -230,7 +234,7 @@ EXPORTED = (
     "gsv_vits_wait", "gsv_t2s_prefetch", "gsv_t2s_generate_start", "gsv_t2s_generate_finish",
     "gsv_vits_decode_batch_async", "gsv_vits_batch_wait", "gsv_ref_encode", "gsv_roberta_batch",
     "gsv_f16_exact", "gsv_request_stop", "gsv_debug_hbm_copy", "gsv_vits_frames", "gsv_vits_decode_item",
-    "gsv_debug_interp_linear",
+    "gsv_debug_interp_linear", "gsv_t2s_generate_each", "gsv_debug_sample_each",
 )
 
 
@@ -339,6 +343,39 @@ def debug_sample(logits, seen, sampler: "Sampler", step: int):
     return tok, stop
 
 
+def _each_args(n: int, samplers, streams):
+    """The (samplers, streams) arrays of a per-sequence call over n sequences: one Sampler per
+    sequence; streams None (the slot numbering) or n integers >= 0.  ValueError otherwise."""
+    samplers = list(samplers)
+    if len(samplers) != n:
+        raise ValueError(f"samplers: {len(samplers)} entries for {n} sequences")
+    if not all(isinstance(sp, Sampler) for sp in samplers):
+        raise ValueError("samplers: every entry must be a Sampler")
+    sarr = (Sampler * n)(*samplers)
+    if streams is None:
+        return sarr, None
+    streams = list(streams)
+    if len(streams) != n:
+        raise ValueError(f"streams: {len(streams)} entries for {n} sequences")
+    for i, v in enumerate(streams):
+        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < 1 << 31:
+            raise ValueError(f"streams[{i}] must be an integer in [0, 2^31), got {v!r}")
+    return sarr, (ctypes.c_int32 * n)(*[int(v) for v in streams])
+
+
+def debug_sample_each(logits, seen, samplers, step: int, streams=None):
+    """debug_sample with one Sampler (and Philox stream; None: the row index) per row
+    (gsv_debug_sample_each)."""
+    torch = _torch()
+    B = logits.shape[0]
+    sarr, starr = _each_args(B, samplers, streams)
+    tok = torch.empty((B,), dtype=torch.int64, device=logits.device)
+    stop = torch.empty((B,), dtype=torch.uint8, device=logits.device)
+    _check(lib().gsv_debug_sample_each(_ptr(logits), _ptr(seen), B, sarr, starr, step, _ptr(tok), _ptr(stop),
+                                       _stream()), "gsv_debug_sample_each")
+    return tok, stop
+
+
 class Engine:
     """One engine per GPU process, holding one character's weights."""
 
@@ -430,18 +467,39 @@ class Engine:
         return x, prompts
 
     def t2s_generate(self, utts: Sequence[Tuple], sampler: Optional[Sampler] = None,
-                     out_stride: int = 1024) -> List[np.ndarray]:
+                     out_stride: int = 1024, *, samplers: Optional[Sequence[Sampler]] = None,
+                     streams: Optional[Sequence[int]] = None) -> List[np.ndarray]:
         """utts: sequence of (ref_seq, text_seq, ref_bert, text_bert, ssl[, force_steps]);
-        force_steps > 0 runs that utterance for exactly that many loop steps (EOS ignored)."""
+        force_steps > 0 runs that utterance for exactly that many loop steps (EOS ignored).
+
+        samplers: one Sampler per utterance instead of `sampler` (gsv_t2s_generate_each: one
+        launch, every sequence sampling with its own controls; max_steps equal in all).
+        streams: with samplers, the Philox stream word per utterance (None: its slot, as
+        without samplers; 0: the noise of a batch-1 generate).  ValueError for a wrong length,
+        a bad stream or both sampler arguments."""
+        if samplers is None:
+            if streams is not None:
+                raise ValueError("streams needs samplers")
+        else:
+            if sampler is not None:
+                raise ValueError("sampler and samplers are exclusive")
+            sarr, starr = _each_args(len(utts), samplers, streams)   # (validates the whole lists)
         if len(utts) > MAX_BATCH:   # the engine decodes up to 64 sequences together
             out = []
             for i in range(0, len(utts), MAX_BATCH):
-                out += self.t2s_generate(utts[i:i + MAX_BATCH], sampler, out_stride)
+                j = i + MAX_BATCH
+                if samplers is None:
+                    out += self.t2s_generate(utts[i:j], sampler, out_stride)
+                else:
+                    out += self.t2s_generate(utts[i:j], None, out_stride, samplers=list(samplers)[i:j],
+                                             streams=None if streams is None else list(streams)[i:j])
             return out
         arr = (Utt * len(utts))()
         keep = []
         pf = getattr(self, "_pf", [])
         hit = next((j for j, p in enumerate(pf) if len(utts) == 1 and p[0] is utts[0]), None)
+        if samplers is not None:
+            hit = None   # (the engine takes no prefetched utterance on this path)
         # consumed entries go; on a single-utterance miss the engine keeps a queued
         # prefetch (the latest), whose buffers must stay alive; a batch drops all
         self._pf = pf[hit + 1:] if hit is not None else pf[-1:] if len(utts) == 1 else []
@@ -451,9 +509,15 @@ class Engine:
             else:
                 arr[i], k = self.make_utt(*u)
             keep.append(k)
-        sp = sampler or make_sampler()
         out = np.zeros((len(utts), out_stride), dtype=np.int64)
         lens = np.zeros(len(utts), dtype=np.int32)
+        if samplers is not None:
+            _check(lib().gsv_t2s_generate_each(self.h, len(utts), arr, sarr, starr,
+                                               out.ctypes.data_as(ctypes.c_void_p), out_stride,
+                                               lens.ctypes.data_as(ctypes.c_void_p), _stream()),
+                   "gsv_t2s_generate_each")
+            return [out[i, :lens[i]].copy() for i in range(len(utts))]
+        sp = sampler or make_sampler()
         _check(lib().gsv_t2s_generate(self.h, len(utts), arr, ctypes.byref(sp),
                                       out.ctypes.data_as(ctypes.c_void_p), out_stride,
                                       lens.ctypes.data_as(ctypes.c_void_p), _stream()),

@@ -257,26 +257,33 @@ class GENIE:
         return np.expand_dims(y[:, -idx:], axis=0)
 
     def tts_batch(self, items: Sequence[tuple], prompt_audio: ReferenceAudio, model, sampler: Sampler,
-                  speed: Union[float, Sequence[float]] = 1.0) -> List[np.ndarray]:
+                  speed: Union[float, Sequence[float]] = 1.0, samplers: Optional[Sequence[Sampler]] = None,
+                  streams: Optional[Sequence[int]] = None) -> List[np.ndarray]:
         """Batched synthesis for one character and reference: items are
         (text_seq, text_bert|None[, force_steps]).  All sequences decode together
         (one multi-sequence persistent launch, ragged: a finished sequence drops out);
         the vocoder runs each utterance's text/flow part on concurrent lanes and the
         generator once over the whole batch (gsv_vits_decode_batch).  speed: one speech rate
-        for all items, or one per item."""
-        toks = self.tts_batch_t2s(items, prompt_audio, model, sampler)
+        for all items, or one per item.  samplers / streams: one sampler (and Philox stream) per
+        item instead of `sampler`, still one launch (Engine.t2s_generate)."""
+        toks = (self.tts_batch_t2s(items, prompt_audio, model, sampler) if samplers is None and streams is None
+                else self.tts_batch_t2s(items, prompt_audio, model, sampler, samplers=samplers, streams=streams))
         wavs = self.tts_batch_vocoder(items, toks, prompt_audio, model, speed=speed)
         return [w if isinstance(w, np.ndarray) else w.cpu().numpy() for w in wavs]
 
-    def tts_batch_t2s(self, items: Sequence[tuple], prompt_audio: ReferenceAudio, model, sampler: Sampler):
-        """The T2S half of tts_batch: one ragged batched generate -> token arrays."""
+    def tts_batch_t2s(self, items: Sequence[tuple], prompt_audio: ReferenceAudio, model, sampler: Sampler,
+                      samplers: Optional[Sequence[Sampler]] = None, streams: Optional[Sequence[int]] = None):
+        """The T2S half of tts_batch: one ragged batched generate -> token arrays.  samplers:
+        one per item, used instead of `sampler`; streams: their Philox stream words."""
         ssl = np.asarray(prompt_audio.ssl_content, np.float32).reshape(768, -1)
         utts = [(prompt_audio.phonemes_seq, it[0], prompt_audio.text_bert, it[1], ssl,
                  it[2] if len(it) > 2 else 0) for it in items]
         # one generate for the whole batch: the engine's multi-sequence persistent decode
         # (B <= 64) costs ~2 ms per extra sequence over a single one
         # (profiles/r03i_batch_sweep.json), so splitting never pays
-        return model.ENGINE.t2s_generate(utts, sampler)
+        if samplers is None and streams is None:
+            return model.ENGINE.t2s_generate(utts, sampler)
+        return model.ENGINE.t2s_generate(utts, None, samplers=samplers, streams=streams)
 
     def tts_batch_vocoder(self, items: Sequence[tuple], toks, prompt_audio: ReferenceAudio, model,
                           overlapped: bool = False, speed: Union[float, Sequence[float]] = 1.0):

@@ -73,6 +73,7 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
         model_manager.vits_noise = cfg["noise"]
     splitter = TextSplitter()
     pipeline = bool(cfg.get("pipeline", False))
+    mixed = bool(cfg.get("mixed_sampling", False))
     pending: List[dict] = []        # tts requests: {"id", "character_name", "sentences", "next", "force_steps"}
 
     def reply(**kw):
@@ -180,7 +181,13 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
         (gsv_vits_decode_batch_async), whose chunks are streamed once this T2S is done; with
         nothing left to start, the vocoder is joined at once.  Off by default: measured on
         one MI355X it raised p50 first audio (50 QPS: 47 -> 58 ms) without raising the
-        saturated rate (profiles/r02g_server_qps_pipeline.json)."""
+        saturated rate (profiles/r02g_server_qps_pipeline.json).
+
+        With cfg["mixed_sampling"] a round takes the ready requests of one character whatever
+        their controls: each brings its own sampler into one batched generate (the character's
+        when it gave no control).  A request that gave a seed samples on Philox stream 0 -- the
+        noise tts(..., seed=) draws alone, whatever else is in the round -- the others on their
+        position in the round."""
         ready = [r for r in pending if r["next"] < len(r["sentences"])]
         if not ready:
             finish_inflight()
@@ -194,7 +201,11 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
             resolve_sampler(r, m)
             sp = r["sampler"] or own
             return None if sp is None else sampler_key(sp)
-        group = [r for r in group if skey(r) == skey(group[0])]
+        if mixed:
+            for r in group:
+                resolve_sampler(r, m)
+        else:
+            group = [r for r in group if skey(r) == skey(group[0])]
         group = group[:round_size(len(group))]
         idx = [r["next"] for r in group]
         try:
@@ -206,7 +217,12 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
                 ts, tb = api._g2p("。" + r["sentences"][r["next"]], m.LANGUAGE)      # Inference.py:27-28
                 items.append((ts, tb, r["force_steps"]))
             tts_client.stop_event.clear()
-            toks = tts_client.tts_batch_t2s(items, ref, m, group[0]["sampler"] or own)
+            if mixed:
+                each = [r["sampler"] or own or make_sampler() for r in group]
+                streams = [0 if "seed" in r["sampling"] else i for i, r in enumerate(group)]
+                toks = tts_client.tts_batch_t2s(items, ref, m, None, samplers=each, streams=streams)
+            else:
+                toks = tts_client.tts_batch_t2s(items, ref, m, group[0]["sampler"] or own)
             finish_inflight()
             eng = m.ENGINE if getattr(m.VITS, "engine", None) is m.ENGINE else None
             overlapped = pipeline and eng is not None
@@ -263,10 +279,11 @@ class Router:
 
     def __init__(self, gpus: List[int], g2p: Optional[str] = None, ssl: Optional[str] = None,
                  sv: Optional[str] = None, greedy: bool = False, worker=None, pipeline: bool = False,
-                 noise: Optional[str] = None):
+                 noise: Optional[str] = None, mixed_sampling: bool = False):
         self.gpus = gpus
         self.worker = worker or _worker_main         # tests substitute a host-only worker
-        self.cfg = {"g2p": g2p, "ssl": ssl, "sv": sv, "greedy": greedy, "pipeline": pipeline, "noise": noise}
+        self.cfg = {"g2p": g2p, "ssl": ssl, "sv": sv, "greedy": greedy, "pipeline": pipeline, "noise": noise,
+                    "mixed_sampling": mixed_sampling}
         self.ids = itertools.count(1)
         self.loop: Optional[asyncio.AbstractEventLoop] = None
         self.queues: Dict[int, asyncio.Queue] = {}
@@ -520,13 +537,15 @@ def create_app(router: Router):
 
 
 def start_server(host: str = "127.0.0.1", port: int = 8000, gpus: Optional[List[int]] = None,
-                 g2p: Optional[str] = None, ssl: Optional[str] = None, sv: Optional[str] = None) -> None:
-    """Server.py:174-175 with one engine worker per GPU instead of uvicorn workers."""
+                 g2p: Optional[str] = None, ssl: Optional[str] = None, sv: Optional[str] = None,
+                 mixed_sampling: bool = False) -> None:
+    """Server.py:174-175 with one engine worker per GPU instead of uvicorn workers.
+    mixed_sampling: requests whose sampling controls differ share a round (run_round)."""
     import uvicorn
     if gpus is None:
         n = int(os.environ.get("GENIE_GPUS", "1"))
         gpus = list(range(n))
-    router = Router(gpus, g2p=g2p, ssl=ssl, sv=sv)
+    router = Router(gpus, g2p=g2p, ssl=ssl, sv=sv, mixed_sampling=mixed_sampling)
     try:
         uvicorn.run(create_app(router), host=host, port=port, workers=1)
     finally:
@@ -542,5 +561,7 @@ if __name__ == "__main__":
     ap.add_argument("--g2p")
     ap.add_argument("--ssl")
     ap.add_argument("--sv")
+    ap.add_argument("--mixed-sampling", action="store_true",
+                    help="requests whose sampling controls differ share a round (one sampler per sequence)")
     a = ap.parse_args()
-    start_server(a.host, a.port, list(range(a.gpus)), a.g2p, a.ssl, a.sv)
+    start_server(a.host, a.port, list(range(a.gpus)), a.g2p, a.ssl, a.sv, a.mixed_sampling)

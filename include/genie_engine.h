@@ -157,6 +157,37 @@ int gsv_t2s_encode(gsv_engine* eng, const gsv_utt* u, float* x, int64_t* prompts
 int gsv_t2s_generate(gsv_engine* eng, int batch, const gsv_utt* utts, const gsv_sampler* s,
                      int64_t* out_tokens, int32_t out_stride, int32_t* out_len, void* stream);
 
+/* gsv_t2s_generate with one sampler per sequence: samplers[b] is sequence b's, in one launch.
+ * The decode kernels read a device table of batch entries (top_k, temperature,
+ * repetition_penalty, top_p, greedy, seed and the stream word) at every sampler site: the
+ * prefill's first-stage sampler, the persistent kernels, the per-step graphs and a re-run on them.
+ *
+ * The stream word: the Philox counter of the sampling noise is (token index, loop step,
+ * stream, 0x51) under the key `seed`.  gsv_t2s_generate fills `stream` with the batch slot, so a
+ * sampled sentence in slot i > 0 draws other noise than alone in slot 0.  Here streams[b] is
+ * that word for sequence b (>= 0; NULL: streams[b] = b, the numbering of gsv_t2s_generate).
+ * A sequence with streams[b] = 0 draws what a batch-1 generate with its sampler draws, whatever
+ * slot it is in and whatever else is in the batch.
+ *
+ * Every entry is checked as gsv_t2s_generate checks its sampler; a bad one gives GSV_E_ARG and
+ * the message names its index.  max_steps is launch-wide: it must be equal in all entries
+ * (GSV_E_ARG otherwise).  An entry's force_steps is that sequence's forced length unless its
+ * gsv_utt.force_steps is set, which wins, as in gsv_t2s_generate.
+ *
+ * Greedy: the fused-argmax step end is a launch-wide mode.  It runs only when every entry is
+ * greedy with one repetition_penalty and one temperature; then the launch is exactly
+ * gsv_t2s_generate's.  Otherwise the launch runs the sampler workgroups and a greedy entry takes
+ * the sampler's own greedy branch: the argmax of penalised / temperature, where the fused step
+ * end takes the argmax of penalised.  These are the same tokens at temperature 1; at another
+ * temperature the division could break a tie of two nearly equal logits differently.
+ *
+ * With equal entries and streams NULL the tokens are gsv_t2s_generate's, bit for bit.  A
+ * prefetched utterance (gsv_t2s_prefetch) is not taken by this call. */
+int gsv_t2s_generate_each(gsv_engine* eng, int batch, const gsv_utt* utts,
+                          const gsv_sampler* samplers /* [batch] */,
+                          const int32_t* streams      /* [batch], or NULL: streams[b] = b */,
+                          int64_t* out_tokens, int32_t out_stride, int32_t* out_len, void* stream);
+
 /* Parity/session entry points mirroring the reference graphs one call at a time.
  * prefill: x (device [L,512]), prompts (device [P]) -> writes slot `seq` of the
  *   engine KV cache, y (device i64 [P+1]), logits (device f32 [1025], may be NULL).
@@ -386,6 +417,10 @@ int gsv_debug_ktrace(gsv_engine* eng, uint64_t* host, int n);
  * (Philox counter); tokens (device i64 [B]) and stop flags (device u8 [B]). */
 int gsv_debug_sample(const float* logits, const uint32_t* seen, int B, const gsv_sampler* s,
                      int step, int64_t* tokens, uint8_t* stop, void* stream);
+/* The same launch with a per-row sampler table (gsv_t2s_generate_each): samplers (host [B]),
+ * streams (host [B], or NULL: streams[b] = b). */
+int gsv_debug_sample_each(const float* logits, const uint32_t* seen, int B, const gsv_sampler* samplers,
+                          const int32_t* streams, int step, int64_t* tokens, uint8_t* stop, void* stream);
 
 /* Probe: replay one kernel configuration `iters` times (hipGraph) between HIP
  * events on the engine stream; *us = average microseconds per launch.

@@ -7,7 +7,10 @@ G2P / SSL stand-ins (genie_tts_amd/stubs.py); every sentence is forced to 81 loo
 steps = 80 semantic tokens = 3.2 s of audio (random weights never emit EOS).
 
 Usage: python tools/qps_sweep.py [--gpus N] [--qps 5,10,20,40,80] [--requests 1000] [--pipeline 0|1]
-Prints one JSON line.
+                                 [--seeds 0|1] [--mixed-sampling 0|1]
+--seeds 1: sampled decoding, every request with a seed of its own (what a client that wants
+repeatable audio sends); --mixed-sampling 1: the server's mixed_sampling switch (such requests
+share a round).  Prints one JSON line.
 """
 import argparse
 import asyncio
@@ -39,10 +42,12 @@ async def main():
     ap.add_argument("--port", type=int, default=8765)
     ap.add_argument("--pipeline", type=int, default=0,
                     help="workers overlap each round's vocoder with the next round's T2S")
+    ap.add_argument("--seeds", type=int, default=0, help="1: sampled decoding, a seed per request")
+    ap.add_argument("--mixed-sampling", type=int, default=0, help="the server's mixed_sampling switch")
     a = ap.parse_args()
 
     router = Router(list(range(a.gpus)), g2p="genie_tts_amd.stubs:toy_g2p", ssl="genie_tts_amd.stubs:toy_ssl",
-                    greedy=True, pipeline=bool(a.pipeline))
+                    greedy=not a.seeds, pipeline=bool(a.pipeline), mixed_sampling=bool(a.mixed_sampling))
     loop = asyncio.get_running_loop()
     t0 = time.time()
     router.start(loop)
@@ -66,12 +71,15 @@ async def main():
         assert r.status_code == 200, r.text
         startup_s = time.time() - t0
 
+        seeds = iter(range(1, 1 << 30))
+
         async def one(text, lat, done):
             t = time.perf_counter()
             first = None
             n = 0
+            ctl = dict(seed=next(seeds)) if a.seeds else {}
             async with cl.stream("POST", base + "/tts", json=dict(character_name="bench", text=text,
-                                                                  force_steps=81)) as resp:
+                                                                  force_steps=81, **ctl)) as resp:
                 assert resp.status_code == 200
                 async for chunk in resp.aiter_bytes():
                     if first is None:
@@ -112,7 +120,8 @@ async def main():
     router.close()
     print(json.dumps({"workload": "configs[4]: FastAPI router + engine worker per GPU, Poisson QPS sweep, "
                                   "1 sentence (80 tokens, 3.2 s audio) per request",
-                      "gpus": a.gpus, "startup_s": startup_s, "sweep": out}), flush=True)
+                      "gpus": a.gpus, "per_request_seeds": bool(a.seeds), "mixed_sampling": bool(a.mixed_sampling),
+                      "startup_s": startup_s, "sweep": out}), flush=True)
 
 
 if __name__ == "__main__":
