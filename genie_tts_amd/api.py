@@ -241,6 +241,15 @@ def _rate(speed) -> dict:
     return {} if float(speed) == 1.0 else {"speed": float(speed)}
 
 
+def _out_rate(sample_rate, pcm16: bool = False) -> dict:
+    """The output-format keywords of a synthesis call: nothing when sample_rate is None (today's
+    call, unchanged), ValueError for a rate the engine's output stage does not have."""
+    if sample_rate is None:
+        return {}
+    from .engine import check_out_format
+    return check_out_format(sample_rate, pcm16)
+
+
 def _sampling(top_k=None, top_p=None, temperature=None, repetition_penalty=None, seed=None) -> dict:
     """The sampling keywords of a synthesis call that were given, validated (ValueError for
     a value the engine rejects) before anything is synthesized."""
@@ -263,7 +272,8 @@ def _resolve_sampler(character_name: str, sampler, fields: dict):
     return override_sampler(sampler, **fields)
 
 
-def _synthesize(character_name: str, sentence, text_bert=None, sampler=None, speed: float = 1.0) -> np.ndarray:
+def _synthesize(character_name: str, sentence, text_bert=None, sampler=None, speed: float = 1.0,
+                **fmt) -> np.ndarray:
     m = model_manager.get(character_name)
     if m is None:
         raise ValueError(f"character '{character_name}' is not loaded")
@@ -277,14 +287,15 @@ def _synthesize(character_name: str, sentence, text_bert=None, sampler=None, spe
         return None
     return tts_client.tts(sentence, ref, m.T2S_ENCODER, m.T2S_FIRST_STAGE_DECODER, m.T2S_STAGE_DECODER, m.VITS,
                           m.PROMPT_ENCODER, m.LANGUAGE, text_bert=text_bert, g2p=_g2p, sampler=sampler,
-                          **_rate(speed))
+                          **_rate(speed), **fmt)
 
 
-def _synthesize_all(character_name: str, sentences: List, text_bert=None, sampler=None, speed: float = 1.0):
+def _synthesize_all(character_name: str, sentences: List, text_bert=None, sampler=None, speed: float = 1.0,
+                    **fmt):
     """Every sentence, in order; on the engine the vocoder of one sentence overlaps the
     T2S of the next (GENIE.tts_stream)."""
     if len(sentences) < 2:
-        return [_synthesize(character_name, s, text_bert, sampler, **_rate(speed)) for s in sentences]
+        return [_synthesize(character_name, s, text_bert, sampler, **_rate(speed), **fmt) for s in sentences]
     m = model_manager.get(character_name)
     if m is None:
         raise ValueError(f"character '{character_name}' is not loaded")
@@ -298,31 +309,50 @@ def _synthesize_all(character_name: str, sentences: List, text_bert=None, sample
         return []
     return list(tts_client.tts_stream(sentences, ref, m.T2S_ENCODER, m.T2S_FIRST_STAGE_DECODER, m.T2S_STAGE_DECODER,
                                       m.VITS, m.PROMPT_ENCODER, m.LANGUAGE, text_bert=text_bert, g2p=_g2p,
-                                      sampler=sampler, vocoder_cus=VOCODER_CUS, **_rate(speed)))
+                                      sampler=sampler, vocoder_cus=VOCODER_CUS, **_rate(speed), **fmt))
 
 
-def _play(audio: np.ndarray) -> None:
+def _play(audio: np.ndarray, sample_rate: int = SAMPLE_RATE) -> None:
     try:
         import sounddevice as sd   # noqa: F401  (absent here, as on most servers)
-        sd.play(np.asarray(audio, np.float32).squeeze(), SAMPLE_RATE)
+        sd.play(np.asarray(audio, np.float32).squeeze(), sample_rate)
         sd.wait()
     except Exception as e:      # TTSPlayer.py:136-146: playback skipped, synthesis goes on
         logger.warning("Failed to initialize sounddevice: %s. Audio playback will be skipped.", e)
+
+
+def _write_pcm16_wav(path: str, pcm: bytes, sample_rate: int) -> None:
+    """A 16-bit mono WAV from samples that are already int16 (the GPU's output stage)."""
+    import wave
+    parent = os.path.dirname(path)
+    if parent:
+        os.makedirs(parent, exist_ok=True)
+    with wave.open(path, "wb") as wf:
+        wf.setnchannels(1)
+        wf.setsampwidth(2)
+        wf.setframerate(sample_rate)
+        wf.writeframes(pcm)
 
 
 def tts(character_name: str, text: Union[str, Sequence[int], np.ndarray], play: bool = False,
         split_sentence: bool = True, save_path: Union[str, os.PathLike, None] = None,
         text_bert: Optional[np.ndarray] = None, sampler=None, speed: float = 1.0, *,
         top_k: Optional[int] = None, top_p: Optional[float] = None, temperature: Optional[float] = None,
-        repetition_penalty: Optional[float] = None, seed: Optional[int] = None) -> Optional[np.ndarray]:
+        repetition_penalty: Optional[float] = None, seed: Optional[int] = None,
+        sample_rate: Optional[int] = None) -> Optional[np.ndarray]:
     """Internal.py:265-310 (TTSPlayer session: split, synthesize each sentence, save the
     concatenation as 16-bit WAV).  Returns the audio f32 [sum 1280*G_i] at 32 kHz.
+    sample_rate: 8000, 16000, 22050, 24000, 32000, 44100 or 48000 (ValueError otherwise): the audio
+    is returned, saved (the WAV header carries the rate) and played at that rate, each sentence
+    resampled on the GPU behind its vocoder (Engine.audio_convert); None: 32 kHz, today's path.
     speed: the speech rate (GPT-SoVITS's `speed`, 0.25 .. 4; ValueError otherwise): sentence i
     is 640 * Engine.vits_frames(G_i, speed) samples, its pitch unchanged.
     top_k (1..64), top_p (0 < p <= 1, nucleus sampling), temperature (> 0), repetition_penalty
     (> 0), seed: GPT-SoVITS's sampling controls; None keeps the field of `sampler` (or, without
     one, of the character's sampler), a value overrides it on a copy.  ValueError for a bad value."""
     rate = _rate(speed)
+    rate.update(_out_rate(sample_rate))
+    out_rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
     fields = _sampling(top_k, top_p, temperature, repetition_penalty, seed)
     if character_name not in _reference_audios:
         logger.error("Please call 'set_reference_audio' first to set the reference audio.")
@@ -336,9 +366,9 @@ def tts(character_name: str, text: Union[str, Sequence[int], np.ndarray], play: 
     if _session_stop.is_set():               # stopped: the session's STREAM_END (and its save) never runs
         return audio
     if save_path:
-        A.write_wav(os.fspath(save_path), audio, SAMPLE_RATE)
+        A.write_wav(os.fspath(save_path), audio, out_rate)
     if play:
-        _play(audio)
+        _play(audio, out_rate)
     return audio
 
 
@@ -346,11 +376,15 @@ async def tts_async(character_name: str, text: str, play: bool = False, split_se
                     save_path: Union[str, os.PathLike, None] = None, speed: float = 1.0, *, sampler=None,
                     top_k: Optional[int] = None, top_p: Optional[float] = None,
                     temperature: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                    seed: Optional[int] = None) -> AsyncIterator[bytes]:
+                    seed: Optional[int] = None, sample_rate: Optional[int] = None) -> AsyncIterator[bytes]:
     """Internal.py:193-262: yields one raw 16-bit PCM chunk per sentence as soon as it
     is synthesized (TTSPlayer chunk callback), the engine running off the event loop.
-    speed, sampler and the sampling keywords: as for tts."""
+    speed, sampler and the sampling keywords: as for tts.  sample_rate (as for tts): the chunks
+    are the int16 samples at that rate as the GPU's output stage wrote them (32000 gives the
+    bytes of the call without it); None: today's path, converted on the host."""
     rate = _rate(speed)
+    rate.update(_out_rate(sample_rate, pcm16=True))
+    out_rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
     fields = _sampling(top_k, top_p, temperature, repetition_penalty, seed)
     if character_name not in _reference_audios:
         raise ValueError("Please call 'set_reference_audio' first to set the reference audio.")
@@ -370,11 +404,21 @@ async def tts_async(character_name: str, text: str, play: bool = False, split_se
         if audio is None:
             continue
         chunks.append(audio)
+        if sample_rate is not None:          # int16 from the GPU
+            audio = np.ascontiguousarray(audio, np.int16).reshape(-1)
+            if play:
+                await loop.run_in_executor(None, _play, audio.astype(np.float32) / 32767.0, out_rate)
+            yield audio.tobytes()
+            continue
         if play:
             await loop.run_in_executor(None, _play, audio)
         yield A.to_pcm16(audio)
     if save_path and chunks:
-        A.write_wav(os.fspath(save_path), np.concatenate(chunks), SAMPLE_RATE)
+        if sample_rate is not None:
+            _write_pcm16_wav(os.fspath(save_path), b"".join(np.ascontiguousarray(c, np.int16).tobytes()
+                                                            for c in chunks), out_rate)
+        else:
+            A.write_wav(os.fspath(save_path), np.concatenate(chunks), SAMPLE_RATE)
 
 
 def wait_for_playback_done() -> None:

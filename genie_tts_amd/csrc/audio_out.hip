@@ -1,0 +1,210 @@
+// The output stage: sample rate and 16-bit PCM (include/genie_engine.h, gsv_audio_convert).
+// A rational polyphase resample of the 32 kHz float32 audio with scipy.signal.resample_poly's
+// default filter (Kaiser 5.0 windowed sinc, 10 * max(up, down) taps a side), restated here so
+// nothing depends on scipy at run time, then the optional int16 conversion.  The reference
+// delivers (x * 32767).astype(int16) chunks at 32 kHz only (Core/TTSPlayer.py).
+#include "audio_out.h"
+
+#include <cmath>
+#include <numeric>
+
+#include "engine_internal.h"
+
+using namespace gsv;
+
+namespace {
+
+constexpr int RATES[AO_RATES] = {8000, 16000, 22050, 24000, 32000, 44100, 48000};
+
+double bessel_i0(double x) {   // the power series sum_k ((x / 2)^k / k!)^2
+    const double y = x * x / 4;
+    double term = 1, sum = 1;
+    for (int k = 1; k < 200; ++k) {
+        term *= y / ((double)k * k);
+        sum += term;
+        if (term < 1e-20 * sum) break;
+    }
+    return sum;
+}
+
+// One block: AO_TILE consecutive outputs of item blockIdx.y.  The input window those outputs
+// need is staged in LDS with the zeros outside [0, n_in) written explicitly, so an item never
+// reads its neighbour in a packed buffer.  Each output is one float32 fma chain over ascending
+// n whatever the tile: the same bits from every entry point.
+__global__ __launch_bounds__(AO_TILE) void k_audio_out(AudioRates R, const AudioOutItem* __restrict__ items) {
+    __shared__ float xs[AO_WIN];
+    const AudioOutItem it = items[blockIdx.y];
+    const int k0 = blockIdx.x * AO_TILE;
+    if (k0 >= it.n_out) return;
+    const int k = k0 + (int)threadIdx.x;
+    const int up = R.up[it.rate], down = R.down[it.rate];
+    float y = 0.f;
+    if (up == down) {   // 32000: a copy (n_out == n_in)
+        if (k < it.n_out) y = it.src[k];
+    } else {
+        const int half = R.half[it.rate], q = R.q[it.rate];
+        const float* __restrict__ tab = R.tab[it.rate];
+        const int k1 = min(k0 + AO_TILE, it.n_out) - 1;   // the tile's last output
+        const long long lo = ((long long)k0 * down + half) / up - (q - 1);
+        const long long hi = ((long long)k1 * down + half) / up;
+        const int win = min((int)(hi - lo + 1), AO_WIN);   // (<= AO_WIN for every supported rate)
+        for (int i = threadIdx.x; i < win; i += AO_TILE) {
+            const long long n = lo + i;
+            xs[i] = n >= 0 && n < it.n_in ? it.src[n] : 0.f;
+        }
+        __syncthreads();
+        if (k < it.n_out) {
+            const long long t = (long long)k * down + half;
+            const long long n1 = t / up;
+            const float* __restrict__ c = tab + (size_t)(t - n1 * up) * q;
+            const float* x = xs + (int)(n1 - (q - 1) - lo);
+            for (int i = 0; i < q; ++i) y = fmaf(c[i], x[i], y);
+        }
+    }
+    if (k >= it.n_out) return;
+    if (it.format == 0) {
+        ((float*)it.dst)[k] = y;
+    } else {   // (x * 32767).astype(int16) of the reference, saturated
+        const float v = fminf(fmaxf(y * 32767.0f, -32768.0f), 32767.0f);
+        ((int16_t*)it.dst)[k] = (int16_t)(int)v;
+    }
+}
+
+}  // namespace
+
+int gsv::audio_rate_index(int out_rate) {
+    if (out_rate == 0) out_rate = 32000;
+    for (int i = 0; i < AO_RATES; ++i)
+        if (RATES[i] == out_rate) return i;
+    return -1;
+}
+
+long long gsv::audio_samples(int n_in, int out_rate) {
+    const int i = audio_rate_index(out_rate);
+    if (i < 0 || n_in < 0) return -1;
+    const int g = std::gcd(32000, RATES[i]);
+    const long long up = RATES[i] / g, down = 32000 / g;
+    return ((long long)n_in * up + down - 1) / down;
+}
+
+void gsv::audio_rate_params(AudioRates* r) {
+    for (int i = 0; i < AO_RATES; ++i) {
+        const int g = std::gcd(32000, RATES[i]);
+        r->tab[i] = nullptr;
+        r->up[i] = RATES[i] / g;
+        r->down[i] = 32000 / g;
+        r->half[i] = 10 * std::max(r->up[i], r->down[i]);
+        r->q[i] = (2 * r->half[i] + 1 + r->up[i] - 1) / r->up[i];
+    }
+}
+
+std::vector<float> gsv::audio_phase_table(const AudioRates& r, int rate) {
+    const int up = r.up[rate], half = r.half[rate], q = r.q[rate], len = 2 * half + 1;
+    const double m = std::max(up, r.down[rate]), pi = 3.14159265358979323846, i0b = bessel_i0(5.0);
+    std::vector<double> h(len);
+    double sum = 0;
+    for (int i = 0; i < len; ++i) {
+        const double t = (i - half) / m, u = (double)(i - half) / half;
+        const double sinc = i == half ? 1.0 : std::sin(pi * t) / (pi * t);
+        h[i] = (1.0 / m) * sinc * bessel_i0(5.0 * std::sqrt(std::max(0.0, 1.0 - u * u))) / i0b;
+        sum += h[i];
+    }
+    std::vector<float> tab((size_t)up * q, 0.f);
+    for (int p = 0; p < up; ++p)
+        for (int i = 0; i < q; ++i) {
+            const int j = p + (q - 1 - i) * up;
+            if (j < len) tab[(size_t)p * q + i] = (float)(h[j] / sum * up);   // rounded once to float32
+        }
+    return tab;
+}
+
+void gsv::audio_out_launch(const AudioRates& r, const AudioOutItem* items, int n, int max_n_out, hipStream_t s) {
+    if (n <= 0 || max_n_out <= 0) return;
+    const dim3 grid((max_n_out + AO_TILE - 1) / AO_TILE, n);
+    hipLaunchKernelGGL(k_audio_out, grid, dim3(AO_TILE), 0, s, r, items);
+}
+
+// ---------------------------------------------------------------- engine side
+// The six tables (about 22k floats) and the item table are made at engine creation: nothing
+// is allocated or built at first use, so the stage stays out of stream captures.
+int gsv_engine::audio_out_init() {
+    audio_rate_params(&ao_rates);
+    std::unique_lock<std::shared_mutex> cl(gsv::capture_mu);   // synchronous null-stream copies below
+    for (int i = 0; i < AO_RATES; ++i) {
+        if (ao_rates.up[i] == ao_rates.down[i]) continue;
+        const std::vector<float> t = audio_phase_table(ao_rates, i);
+        float* d = (float*)dalloc(t.size() * 4);
+        if (!d || hipMemcpy(d, t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+            return set_error(GSV_E_HIP, "output stage tables");
+        ao_rates.tab[i] = d;
+    }
+    ao_tab = (AudioOutItem*)dalloc(sizeof(AudioOutItem) * AO_SLOTS);
+    if (!ao_tab || hipHostMalloc((void**)&ao_pin, sizeof(AudioOutItem) * AO_SLOTS, hipHostMallocDefault) != hipSuccess)
+        return set_error(GSV_E_HIP, "output stage item table");
+    for (hipEvent_t& e : ao_ev)
+        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess)
+            return set_error(GSV_E_HIP, "output stage events");
+    return 0;
+}
+
+int gsv_engine::audio_item(const gsv_vits_item& u, AudioOutItem* a) const {
+    const int rate = audio_rate_index(u.out_rate), T = vits_frames(u.n_sem, u.speed);
+    if (rate < 0 || u.out_format < 0 || u.out_format > 1 || T < 0) return GSV_E_ARG;
+    const int n_in = 640 * T;
+    *a = AudioOutItem{u.audio, u.out, n_in, (int)audio_samples(n_in, u.out_rate), rate, u.out_format};
+    return 0;
+}
+
+// Convert items[0..n) in one launch per AO_BATCH items on stream s.  `region` names the part of
+// the item table this call site owns (AO_SYNC: the engine stream's synchronous calls, AO_ASYNC:
+// the overlapped vocoder call, AO_BATCH_AT: a batch): a region is refilled only after the launch
+// that last read it has finished, which it has in practice (the wait is for the previous call's
+// stage, and a vocoder pass lies between two of them).
+int gsv_engine::audio_out(const AudioOutItem* items, int n, int region, hipStream_t s) {
+    if (!ao_tab) return set_error(GSV_E_STATE, "output stage not initialised");
+    const int base = region, cap = region == AO_BATCH_AT ? AO_BATCH : 1;   // (a region is its first slot)
+    hipEvent_t ev = ao_ev[region];
+    (void)hipGetLastError();
+    for (int i = 0; i < n; i += cap) {
+        const int m = std::min(cap, n - i);
+        if (hipEventSynchronize(ev) != hipSuccess) return set_error(GSV_E_HIP, "output stage wait");
+        int max_out = 0;
+        for (int j = 0; j < m; ++j) {
+            ao_pin[base + j] = items[i + j];
+            max_out = std::max(max_out, items[i + j].n_out);
+        }
+        hipMemcpyAsync(ao_tab + base, ao_pin + base, sizeof(AudioOutItem) * m, hipMemcpyHostToDevice, s);
+        audio_out_launch(ao_rates, ao_tab + base, m, max_out, s);
+        hipEventRecord(ev, s);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : set_error(GSV_E_HIP, "output stage launch");
+}
+
+// The items of a vocoder call that carry `out`, converted from their final `audio`.
+int gsv_engine::audio_out_items(const gsv_vits_item* it, int n, int region, hipStream_t s) {
+    std::vector<AudioOutItem> a;
+    for (int i = 0; i < n; ++i) {
+        if (!it[i].out) continue;
+        a.emplace_back();
+        if (audio_item(it[i], &a.back())) return set_error(GSV_E_ARG, "bad output rate or format");
+    }
+    return a.empty() ? 0 : audio_out(a.data(), (int)a.size(), region, s);
+}
+
+extern "C" int gsv_audio_samples(int32_t n_in, int32_t out_rate) {
+    const long long n = audio_samples(n_in, out_rate);
+    return n < 0 || n > INT32_MAX ? GSV_E_ARG : (int)n;
+}
+
+extern "C" int gsv_audio_convert(gsv_engine* eng, const float* audio_32k, int32_t n_in, int32_t out_rate,
+                                 int32_t out_format, void* out, void* stream) {
+    if (!eng) return set_error(GSV_E_ARG, "null engine");
+    const int rate = audio_rate_index(out_rate), n_out = gsv_audio_samples(n_in, out_rate);
+    if (rate < 0 || n_out < 0) return set_error(GSV_E_ARG, "out_rate: 8000, 16000, 22050, 24000, 32000, 44100 or 48000");
+    if (out_format < 0 || out_format > 1) return set_error(GSV_E_ARG, "out_format: 0 (float32) or 1 (int16)");
+    if (n_in > 0 && (!audio_32k || !out)) return set_error(GSV_E_ARG, "null audio buffer");
+    hipSetDevice(eng->device);
+    StreamScope sc(eng, stream);
+    const AudioOutItem a{audio_32k, out, n_in, n_out, rate, out_format};
+    return eng->audio_out(&a, 1, gsv_engine::AO_SYNC, sc.st());
+}

@@ -153,6 +153,9 @@ gsv_engine::~gsv_engine() {
     if (sv_ovf_host) hipHostFree(sv_ovf_host);
     if (perr_host) hipHostFree(perr_host);
     if (stop_word) hipHostFree(stop_word);
+    if (ao_pin) hipHostFree(ao_pin);
+    for (hipEvent_t e : ao_ev)
+        if (e) hipEventDestroy(e);
     if (res_pin) hipHostFree(res_pin);
     for (GenSlot& g : gq) {
         if (g.res) hipHostFree(g.res);
@@ -1560,6 +1563,10 @@ extern "C" int gsv_engine_create(int device, int version, gsv_engine** out) {
     for (auto& x : e->ev) hipEventCreate(&x);
     hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming);
     hipEventCreateWithFlags(&e->ev_out, hipEventDisableTiming);
+    if (int r = e->audio_out_init()) {   // the output stage's tables: here, never at first use
+        delete e;
+        return r;
+    }
     *out = e;
     return 0;
 }

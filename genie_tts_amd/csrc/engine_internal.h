@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "lanes.h"
 #include "vits.h"
+#include "audio_out.h"
 
 namespace gsv {
 int set_error(int code, const std::string& msg);
@@ -543,6 +544,18 @@ struct gsv_engine {
     hipError_t host_wait(hipStream_t st);
     int prompt_encode(const float* ref_audio, int n_audio, const float* sv_emb, float* ge,
                       float* ge_adv, hipStream_t st);
+    // ---- output stage (audio_out.hip): sample rate / int16 of a vocoder item's `out`, gsv_audio_convert
+    // The item table's regions, one per call site that may run beside the others: a region's
+    // event follows the launch that last read it.
+    static constexpr int AO_SYNC = 0, AO_ASYNC = 1, AO_BATCH_AT = 2, AO_BATCH = 256, AO_SLOTS = AO_BATCH_AT + AO_BATCH;
+    gsv::AudioRates ao_rates{};        // the rates' phase tables (device), made at engine creation
+    gsv::AudioOutItem* ao_tab = nullptr;   // [AO_SLOTS] device item table, filled per call
+    gsv::AudioOutItem* ao_pin = nullptr;   // its pinned source
+    hipEvent_t ao_ev[3] = {};
+    int audio_out_init();
+    int audio_item(const gsv_vits_item& u, gsv::AudioOutItem* a) const;   // GSV_E_ARG: bad rate / format / speed
+    int audio_out(const gsv::AudioOutItem* items, int n, int region, hipStream_t s);
+    int audio_out_items(const gsv_vits_item* it, int n, int region, hipStream_t s);
 };
 
 namespace gsv {

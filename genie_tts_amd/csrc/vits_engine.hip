@@ -747,6 +747,7 @@ int gsv_engine::vits_launch_queued(hipStream_t s) {
                                  u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0,
                                  vcall_scale, u.audio, s, use_convh ? vovf : nullptr, timing, u.speed))
         return r;
+    if (int r = audio_out_items(&u, 1, AO_ASYNC, s)) return r;   // on the vocoder's stream, behind its pass
     if (use_convh) hipMemcpyAsync(vovf_host, vovf, 4, hipMemcpyDeviceToHost, s);
     hipEventRecord(vev_done, s);
     vpending = true;
@@ -770,6 +771,7 @@ int gsv_engine::vits_wait(hipStream_t caller) {
                                      u.noise_mode == 2 ? u.noise_seed : 0, vcall_scale, u.audio, vlast, nullptr,
                                      timing, u.speed))
             return r;
+        if (int r = audio_out_items(&u, 1, AO_ASYNC, vlast)) return r;   // `out` from the re-run's audio
         hipEventRecord(vev_done, vlast);
         if (hipEventSynchronize(vev_done) != hipSuccess) return set_error(GSV_E_HIP, "overlapped vocoder re-run");
     }
@@ -1170,9 +1172,11 @@ int gsv_engine::vits_decode_batch(int n, const gsv_vits_item* it, float noise_sc
         if (int r = vits_wait(nullptr)) return r;
     if (n == 1) {   // one utterance: the engine stream itself, no lane fork/join
         const gsv_vits_item& u = it[0];
-        return vits_decode(u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge, u.ge_adv,
-                           u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0, noise_scale,
-                           u.audio, s, u.speed);
+        if (int r = vits_decode(u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge, u.ge_adv,
+                                u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0,
+                                noise_scale, u.audio, s, u.speed))
+            return r;
+        return audio_out_items(&u, 1, AO_SYNC, s);
     }
     vb_items.assign(it, it + n);
     if (int r = vits_batch_launch(noise_scale, s, true)) return r;
@@ -1611,7 +1615,9 @@ int gsv_engine::vits_batch_finish(hipStream_t s) {
         hipEventSynchronize(ev[5]);
         hipEventElapsedTime(&ms[3], ev[4], ev[5]);
     }
-    return hipGetLastError() == hipSuccess ? 0 : set_error(GSV_E_HIP, "vocoder batch");
+    if (hipGetLastError() != hipSuccess) return set_error(GSV_E_HIP, "vocoder batch");
+    // the output stage: one launch over the batch's items, behind the re-runs, so from the final audio
+    return audio_out_items(vb_items.data(), n, AO_BATCH_AT, s);
 }
 
 // V2: the reference encoder alone (vits(v2)#79-271: ref spectrogram -> MelStyleEncoder ->
@@ -1667,7 +1673,8 @@ extern "C" int gsv_vits_decode(gsv_engine* eng, const int64_t* text_seq, int32_t
 // An item the vocoder entries accept: its noise source, output buffer and speech rate.
 static bool vits_item_ok(const gsv_vits_item& u) {
     return u.noise_mode >= 0 && u.noise_mode <= 2 && (u.noise_mode != 1 || u.eps) && u.audio &&
-           vits_frames(1, u.speed) > 0;
+           vits_frames(1, u.speed) > 0 &&
+           (!u.out || (audio_rate_index(u.out_rate) >= 0 && u.out_format >= 0 && u.out_format <= 1));
 }
 
 extern "C" int gsv_vits_frames(int32_t n_sem, float speed) { return vits_frames(n_sem, speed); }
@@ -1679,9 +1686,11 @@ extern "C" int gsv_vits_decode_item(gsv_engine* eng, const gsv_vits_item* item, 
     if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
     StreamScope sc(eng, stream);
     const gsv_vits_item& u = *item;
-    return eng->vits_decode(u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge, u.ge_adv,
-                            u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0, noise_scale,
-                            u.audio, sc.st(), u.speed);
+    if (int r = eng->vits_decode(u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge, u.ge_adv,
+                                 u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0,
+                                 noise_scale, u.audio, sc.st(), u.speed))
+        return r;
+    return eng->audio_out_items(&u, 1, gsv_engine::AO_SYNC, sc.st());
 }
 
 extern "C" int gsv_vits_decode_batch(gsv_engine* eng, int32_t n, const gsv_vits_item* items, float noise_scale,

@@ -81,6 +81,8 @@ class VitsItem(ctypes.Structure):
         ("eps", ctypes.c_void_p), ("noise_seed", ctypes.c_uint64), ("noise_mode", ctypes.c_int32),
         ("audio", ctypes.c_void_p),
         ("speed", ctypes.c_float),
+        ("out_rate", ctypes.c_int32), ("out_format", ctypes.c_int32),
+        ("out", ctypes.c_void_p),
     ]
 
 
@@ -181,6 +183,8 @@ def lib():
         L.gsv_vits_frames.argtypes = [i32, ctypes.c_float]
         L.gsv_vits_decode_item.argtypes = [vp, ctypes.POINTER(VitsItem), ctypes.c_float, vp]
         L.gsv_debug_interp_linear.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
+        L.gsv_audio_samples.argtypes = [i32, i32]
+        L.gsv_audio_convert.argtypes = [vp, vp, i32, i32, i32, vp, vp]
         L.gsv_vits_decode_batch_async.argtypes = [vp, i32, ctypes.POINTER(VitsItem), ctypes.c_float, vp]
         L.gsv_vits_batch_wait.argtypes = [vp, vp]
         L.gsv_t2s_prefetch.argtypes = [vp, ctypes.POINTER(Utt), ctypes.POINTER(Sampler), vp]
@@ -235,6 +239,7 @@ EXPORTED = (
     "gsv_vits_decode_batch_async", "gsv_vits_batch_wait", "gsv_ref_encode", "gsv_roberta_batch",
     "gsv_f16_exact", "gsv_request_stop", "gsv_debug_hbm_copy", "gsv_vits_frames", "gsv_vits_decode_item",
     "gsv_debug_interp_linear", "gsv_t2s_generate_each", "gsv_debug_sample_each",
+    "gsv_audio_samples", "gsv_audio_convert",
 )
 
 
@@ -278,12 +283,39 @@ def vits_frames(n_sem: int, speed: float = 1.0) -> int:
     return n
 
 
+SAMPLE_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
+
+
+def audio_samples(n: int, sample_rate: int = 32000) -> int:
+    """Samples of n 32 kHz samples at sample_rate (gsv_audio_samples, the one place the length
+    is computed: ceil(n * up / down)).  ValueError for a rate outside SAMPLE_RATES."""
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, np.integer)) or \
+            int(sample_rate) not in SAMPLE_RATES:
+        raise ValueError(f"sample_rate must be one of {SAMPLE_RATES}, not {sample_rate!r}")
+    m = lib().gsv_audio_samples(int(n), int(sample_rate))
+    if m < 0:
+        raise ValueError(f"no output length for {n!r} samples at {sample_rate!r} Hz")
+    return m
+
+
 def _check(rc: int, what: str):
     if rc != 0:
         msg = lib().gsv_last_error().decode(errors="replace")
         if rc == GSV_E_STOPPED:
             raise EngineStopped(f"{what}: {msg}")
         raise EngineError(f"{what} failed ({rc}): {msg}")
+
+
+def check_out_format(sample_rate=None, pcm16=False) -> dict:
+    """The output-format keys of a vocoder call that were given, validated (ValueError for a
+    rate outside SAMPLE_RATES): nothing when neither is, and the call is then today's."""
+    out = {}
+    if sample_rate is not None:
+        audio_samples(0, sample_rate)
+        out["sample_rate"] = int(sample_rate)
+    if pcm16:
+        out["pcm16"] = True
+    return out
 
 
 def _torch():
@@ -606,20 +638,25 @@ class Engine:
         return self._dev(np.asarray(x).reshape(-1) if not isinstance(x, t.Tensor) else x.reshape(-1), t.int64)
 
     def vits_decode(self, text_seq, pred_semantic, ref_audio=None, ge=None, ge_advanced=None,
-                    eps=None, noise_scale: float = 0.5, noise_seed: Optional[int] = None, speed: float = 1.0):
+                    eps=None, noise_scale: float = 0.5, noise_seed: Optional[int] = None, speed: float = 1.0,
+                    sample_rate: Optional[int] = None, pcm16: bool = False):
         """vits_fp32.onnx for one utterance.  Noise of z_p: eps (tensor/array [192, T']) if
         given, else the engine's Philox N(0,1) stream keyed by noise_seed if given, else zeros.
-        speed: the speech rate (0.25 .. 4; T' = vits_frames(G, speed) frames, 640 T' samples)."""
+        speed: the speech rate (0.25 .. 4; T' = vits_frames(G, speed) frames, 640 T' samples).
+        sample_rate / pcm16: the output stage (see audio_convert) behind the vocoder, on the GPU;
+        the result is then the converted tensor (the 32 kHz float32 one: self.vits_audio_32k[0])."""
+        fmt = check_out_format(sample_rate, pcm16)
         if noise_seed is not None and eps is None:
             return self.vits_decode_batch([dict(text_seq=text_seq, pred_semantic=pred_semantic, ref_audio=ref_audio,
                                                 ge=ge, ge_advanced=ge_advanced, noise_seed=noise_seed,
-                                                speed=speed)], noise_scale)[0]
-        if float(speed) != 1.0:
+                                                speed=speed, **fmt)], noise_scale)[0]
+        if float(speed) != 1.0 or fmt:
             item, keep, audio = self._vits_item(dict(text_seq=text_seq, pred_semantic=pred_semantic,
                                                      ref_audio=ref_audio, ge=ge, ge_advanced=ge_advanced, eps=eps,
-                                                     speed=speed))
+                                                     speed=speed, **fmt))
             _check(lib().gsv_vits_decode_item(self.h, ctypes.byref(item), ctypes.c_float(noise_scale), _stream()),
                    "gsv_vits_decode_item")
+            self.vits_audio_32k = [keep[-1] if item.out else audio]
             return audio
         t = self.torch
         ts = self._ids(text_seq)
@@ -636,8 +673,25 @@ class Engine:
                "gsv_vits_decode")
         return audio
 
+    def audio_convert(self, audio, sample_rate: int = 32000, pcm16: bool = False):
+        """The output stage alone (gsv_audio_convert): 32 kHz float32 audio [n] -> its
+        audio_samples(n, sample_rate) samples at sample_rate (one of SAMPLE_RATES; the polyphase
+        resample of include/genie_engine.h, scipy.signal.resample_poly's default filter), as float32
+        or, with pcm16, saturated int16 ((x * 32767).astype(int16), the reference's chunk format).
+        One launch on the GPU; a device tensor."""
+        t = self.torch
+        a = self._dev(audio, t.float32).reshape(-1)
+        out = t.empty((audio_samples(a.numel(), sample_rate),), dtype=t.int16 if pcm16 else t.float32, device=self.dev)
+        _check(lib().gsv_audio_convert(self.h, _ptr(a), a.numel(), int(sample_rate), int(bool(pcm16)), _ptr(out),
+                                       _stream()), "gsv_audio_convert")
+        return out
+
+    vits_audio_32k: list = []      # the 32 kHz float32 tensors of the last vocoder call, in item order
+
     def _vits_item(self, it: dict):
-        """(VitsItem, tensors it points at, audio tensor) of one vocoder call."""
+        """(VitsItem, tensors it points at, result tensor) of one vocoder call.  With the item
+        keys sample_rate / pcm16 the result is the output stage's tensor (the item's `out`), and
+        the 32 kHz float32 audio, still written, is the last of the kept tensors."""
         t = self.torch
         ts, sem = self._ids(it["text_seq"]), self._ids(it["pred_semantic"])
         G = sem.numel()
@@ -659,7 +713,13 @@ class Engine:
                         0 if ra is None else ra.numel(), 0 if g is None else g.data_ptr(),
                         0 if ga is None else ga.data_ptr(), 0 if e is None else e.data_ptr(),
                         int(seed or 0) & 0xFFFFFFFFFFFFFFFF, mode, audio.data_ptr(), speed)
-        return item, [ts, sem, ra, g, ga, e], audio
+        fmt = check_out_format(it.get("sample_rate"), it.get("pcm16"))
+        if not fmt:
+            return item, [ts, sem, ra, g, ga, e], audio
+        rate, pcm = fmt.get("sample_rate", 32000), bool(fmt.get("pcm16"))
+        out = t.empty((audio_samples(640 * frames, rate),), dtype=t.int16 if pcm else t.float32, device=self.dev)
+        item.out_rate, item.out_format, item.out = rate, int(pcm), out.data_ptr()
+        return item, [ts, sem, ra, g, ga, e, audio], out
 
     @staticmethod
     def vits_frames(n_sem: int, speed: float = 1.0) -> int:
@@ -669,15 +729,19 @@ class Engine:
     def vits_decode_batch(self, items: Sequence[dict], noise_scale: float = 0.5):
         """Several vocoder calls at once (concurrent engine lanes).  Each item: text_seq,
         pred_semantic, and ref_audio (V2) or ge + ge_advanced (V2ProPlus); optional eps or
-        noise_seed, optional speed.  Returns one audio tensor [640 T'] per item (1280 G at speed 1)."""
+        noise_seed, optional speed.  Returns one audio tensor [640 T'] per item (1280 G at speed 1).
+        Optional sample_rate / pcm16 per item: that item's result is the output stage's tensor
+        (one stage launch for the batch); self.vits_audio_32k then holds every item's 32 kHz audio."""
         arr = (VitsItem * len(items))()
-        keep, outs = [], []
+        keep, outs, a32 = [], [], []
         for i, it in enumerate(items):
             arr[i], k, audio = self._vits_item(it)
             keep += k
             outs.append(audio)
+            a32.append(k[-1] if arr[i].out else audio)
         _check(lib().gsv_vits_decode_batch(self.h, len(items), arr, ctypes.c_float(noise_scale), _stream()),
                "gsv_vits_decode_batch")
+        self.vits_audio_32k = a32
         return outs
 
     def vits_decode_batch_async(self, items: Sequence[dict], noise_scale: float = 0.5):
@@ -685,13 +749,15 @@ class Engine:
         beside whatever T2S is issued next.  Returns the audio tensors, valid after
         vits_batch_wait()."""
         arr = (VitsItem * len(items))()
-        keep, outs = [], []
+        keep, outs, a32 = [], [], []
         for i, it in enumerate(items):
             arr[i], k, audio = self._vits_item(it)
             keep += k
             outs.append(audio)
+            a32.append(k[-1] if arr[i].out else audio)
         _check(lib().gsv_vits_decode_batch_async(self.h, len(items), arr, ctypes.c_float(noise_scale),
                                                  _stream()), "gsv_vits_decode_batch_async")
+        self.vits_audio_32k = a32
         # items and device buffers live until the wait -- also a previous batch's, which this
         # call only ordered behind the engine stream (its lanes may still read them)
         # (one generation back: a batch older than the previous one was joined by this launch)
@@ -718,6 +784,7 @@ class Engine:
         _check(lib().gsv_vits_decode_async(self.h, ctypes.byref(it), ctypes.c_float(noise_scale), _stream()),
                "gsv_vits_decode_async")
         self._vits_keep = keep   # device inputs stay alive until the call is finished
+        self.vits_audio_32k = [keep[-1] if it.out else audio]
         return audio
 
     def vits_wait(self):

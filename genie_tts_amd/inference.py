@@ -25,7 +25,7 @@ from typing import Callable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from .engine import EngineStopped, Sampler, request_stop_all, vits_frames
+from .engine import EngineStopped, Sampler, check_out_format, request_stop_all, vits_frames
 from .sessions import (EncoderSession, FirstStageDecoderSession, StageDecoderSession, VitsSession,
                        PromptEncoderSession)
 
@@ -102,10 +102,14 @@ class GENIE:
     def tts(self, text: Union[str, np.ndarray], prompt_audio: ReferenceAudio, encoder, first_stage_decoder,
             stage_decoder, vocoder, prompt_encoder=None, language: str = "japanese",
             text_bert: Optional[np.ndarray] = None, g2p: Optional[Callable] = None,
-            sampler: Optional[Sampler] = None, speed: float = 1.0) -> Optional[np.ndarray]:
-        """speed: the speech rate (0.25 .. 4, GPT-SoVITS's `speed`; 1: the reference's audio)."""
+            sampler: Optional[Sampler] = None, speed: float = 1.0, sample_rate: Optional[int] = None,
+            pcm16: bool = False) -> Optional[np.ndarray]:
+        """speed: the speech rate (0.25 .. 4, GPT-SoVITS's `speed`; 1: the reference's audio).
+        sample_rate (one of engine.SAMPLE_RATES) / pcm16: the audio at that rate and / or as int16,
+        converted on the GPU behind the vocoder (Engine.audio_convert); neither: 32 kHz float32."""
         vits_frames(0, speed)          # ValueError for a bad rate, before any GPU work
         rate = {} if float(speed) == 1.0 else {"speed": float(speed)}
+        rate.update(check_out_format(sample_rate, pcm16))   # ValueError for an unsupported sample rate
         if isinstance(text, str):
             if g2p is None:
                 raise ValueError("text input needs a g2p(text, language) callable (G2P is outside this engine)")
@@ -136,7 +140,8 @@ class GENIE:
     def tts_stream(self, texts: Sequence[Union[str, np.ndarray]], prompt_audio: ReferenceAudio, encoder,
                    first_stage_decoder, stage_decoder, vocoder, prompt_encoder=None, language: str = "japanese",
                    text_bert: Optional[np.ndarray] = None, g2p: Optional[Callable] = None,
-                   sampler: Optional[Sampler] = None, vocoder_cus: int = 64, speed: float = 1.0):
+                   sampler: Optional[Sampler] = None, vocoder_cus: int = 64, speed: float = 1.0,
+                   sample_rate: Optional[int] = None, pcm16: bool = False):
         """tts over a list of sentences, yielding each sentence's audio in order (the
         reference runs them one after the other: TTSPlayer._tts_worker_loop,
         Core/TTSPlayer.py:56-107).  Engine-backed sessions pipeline them: sentence i's
@@ -144,15 +149,17 @@ class GENIE:
         the rest (gsv_vits_decode_async), and sentence i+1's encoder + prefill run on
         those CUs during sentence i's decode (gsv_t2s_prefetch), so sentence i is
         yielded once sentence i+1's T2S is done.  Same tokens and audio as calling
-        tts per sentence.  speed: the speech rate of every sentence."""
+        tts per sentence.  speed: the speech rate of every sentence; sample_rate / pcm16: their
+        output format (as for tts; the stage runs on the vocoder's CUs)."""
         vits_frames(0, speed)          # a bad rate fails here, before anything is started
+        fmt = check_out_format(sample_rate, pcm16)
         eng = _engine_of(encoder, first_stage_decoder, stage_decoder, vocoder)
         if eng is None or vocoder_cus <= 0 or len(texts) < 2:
             for t in texts:
                 if self.stop_event.is_set():
                     return
                 yield self.tts(t, prompt_audio, encoder, first_stage_decoder, stage_decoder, vocoder, prompt_encoder,
-                               language, text_bert, g2p, sampler, speed)
+                               language, text_bert, g2p, sampler, speed, **fmt)
             return
         prev_cus = eng.vocoder_cus     # restored when the stream ends: later single-sentence and
         if prev_cus != vocoder_cus:    # batched calls keep every CU (decode groups, lanes)
@@ -204,7 +211,7 @@ class GENIE:
                     yield done.cpu().numpy()
                 G = sem.size
                 eps = vocoder.eps(G, speed)
-                item = dict(text_seq=text_seq, pred_semantic=sem, speed=speed, **cond)
+                item = dict(text_seq=text_seq, pred_semantic=sem, speed=speed, **cond, **fmt)
                 if eps is not None:
                     item["eps"] = eps
                 else:
@@ -258,17 +265,20 @@ class GENIE:
 
     def tts_batch(self, items: Sequence[tuple], prompt_audio: ReferenceAudio, model, sampler: Sampler,
                   speed: Union[float, Sequence[float]] = 1.0, samplers: Optional[Sequence[Sampler]] = None,
-                  streams: Optional[Sequence[int]] = None) -> List[np.ndarray]:
+                  streams: Optional[Sequence[int]] = None, sample_rate=None, pcm16=False) -> List[np.ndarray]:
         """Batched synthesis for one character and reference: items are
         (text_seq, text_bert|None[, force_steps]).  All sequences decode together
         (one multi-sequence persistent launch, ragged: a finished sequence drops out);
         the vocoder runs each utterance's text/flow part on concurrent lanes and the
         generator once over the whole batch (gsv_vits_decode_batch).  speed: one speech rate
         for all items, or one per item.  samplers / streams: one sampler (and Philox stream) per
-        item instead of `sampler`, still one launch (Engine.t2s_generate)."""
+        item instead of `sampler`, still one launch (Engine.t2s_generate).  sample_rate / pcm16:
+        the output format, one value for all items or one per item (tts_batch_vocoder)."""
         toks = (self.tts_batch_t2s(items, prompt_audio, model, sampler) if samplers is None and streams is None
                 else self.tts_batch_t2s(items, prompt_audio, model, sampler, samplers=samplers, streams=streams))
-        wavs = self.tts_batch_vocoder(items, toks, prompt_audio, model, speed=speed)
+        fmt = {} if sample_rate is None and np.ndim(pcm16) == 0 and not pcm16 else dict(sample_rate=sample_rate,
+                                                                                         pcm16=pcm16)
+        wavs = self.tts_batch_vocoder(items, toks, prompt_audio, model, speed=speed, **fmt)
         return [w if isinstance(w, np.ndarray) else w.cpu().numpy() for w in wavs]
 
     def tts_batch_t2s(self, items: Sequence[tuple], prompt_audio: ReferenceAudio, model, sampler: Sampler,
@@ -286,17 +296,25 @@ class GENIE:
         return model.ENGINE.t2s_generate(utts, None, samplers=samplers, streams=streams)
 
     def tts_batch_vocoder(self, items: Sequence[tuple], toks, prompt_audio: ReferenceAudio, model,
-                          overlapped: bool = False, speed: Union[float, Sequence[float]] = 1.0):
+                          overlapped: bool = False, speed: Union[float, Sequence[float]] = 1.0,
+                          sample_rate=None, pcm16=False):
         """The vocoder half of tts_batch.  overlapped=True (engine-backed vocoder only) starts
         the batch on the vocoder lanes and returns device tensors that are valid after
         model.ENGINE.vits_batch_wait(); the T2S of the next batch runs beside it
-        (gsv_vits_decode_batch_async)."""
+        (gsv_vits_decode_batch_async).  sample_rate (None: 32 kHz float32 as ever) / pcm16: the
+        output format, one value or one per item; a batch may mix rates, and the whole batch is
+        converted by one launch of the engine's output stage."""
         eng = model.ENGINE
         speeds = [float(speed)] * len(items) if np.ndim(speed) == 0 else [float(v) for v in speed]
         if len(speeds) != len(items):
             raise ValueError("speed: one value, or one per item")
         for v in speeds:
             vits_frames(0, v)          # ValueError for a bad rate, before any GPU work
+        rates = [sample_rate] * len(items) if sample_rate is None or np.ndim(sample_rate) == 0 else list(sample_rate)
+        pcms = [bool(pcm16)] * len(items) if np.ndim(pcm16) == 0 else [bool(v) for v in pcm16]
+        if len(rates) != len(items) or len(pcms) != len(items):
+            raise ValueError("sample_rate / pcm16: one value, or one per item")
+        fmts = [check_out_format(r, p) for r, p in zip(rates, pcms)]   # ValueError for an unsupported rate
         if model.PROMPT_ENCODER is not None:
             prompt_audio.update_global_emb(model.PROMPT_ENCODER)
         cond = ({"ref_audio": prompt_audio.audio_32k} if model.PROMPT_ENCODER is None else
@@ -305,11 +323,11 @@ class GENIE:
             cond = model.VITS.v2_cond(prompt_audio.audio_32k)   # the reference branch once per reference
         if getattr(model.VITS, "engine", None) is not eng:
             return [model.VITS.run(None, {"text_seq": it[0], "pred_semantic": tok.reshape(1, 1, -1), **cond,
-                                          **({} if v == 1.0 else {"speed": v})})[0]
-                    for it, tok, v in zip(items, toks, speeds)]
+                                          **({} if v == 1.0 else {"speed": v}), **f})[0]
+                    for it, tok, v, f in zip(items, toks, speeds, fmts)]
         # engine-backed vocoder: all utterances on concurrent lanes (gsv_vits_decode_batch)
-        batch = [dict(text_seq=it[0], pred_semantic=tok, noise_seed=model.VITS.next_seed(), speed=v, **cond)
-                 for it, tok, v in zip(items, toks, speeds)]
+        batch = [dict(text_seq=it[0], pred_semantic=tok, noise_seed=model.VITS.next_seed(), speed=v, **cond, **f)
+                 for it, tok, v, f in zip(items, toks, speeds, fmts)]
         if overlapped:
             return eng.vits_decode_batch_async(batch, model.VITS.noise_scale)
         return eng.vits_decode_batch(batch, model.VITS.noise_scale)

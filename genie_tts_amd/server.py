@@ -9,7 +9,9 @@ CPU ONNX session set, and uvicorn `workers > 1` cannot share its globals).
   POST /tts                           -> the least-loaded worker; StreamingResponse of
                                           raw 16-bit PCM, one chunk per sentence, as
                                           the reference's TTSPlayer chunk callback
-                                          (Server.py:122-143, TTSPlayer.py:98-107)
+                                          (Server.py:122-143, TTSPlayer.py:98-107);
+                                          with `sample_rate` in the payload the chunks are the
+                                          GPU's int16 samples at that rate (X-Sample-Rate)
   POST /stop                          -> every worker
 
 A worker is a spawned process with HIP_VISIBLE_DEVICES set before anything touches
@@ -30,7 +32,7 @@ import multiprocessing as mp
 import os
 import threading
 import time
-from typing import Dict, List, Optional
+from typing import Dict, List, Literal, Optional
 
 logger = logging.getLogger(__name__)
 
@@ -58,8 +60,8 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
     import numpy as np
     import genie_tts_amd as genie
     from genie_tts_amd import api, audio as A
-    from genie_tts_amd.engine import (SAMPLING_FIELDS, check_sampling, make_sampler, override_sampler, sampler_key,
-                                      vits_frames)
+    from genie_tts_amd.engine import (SAMPLING_FIELDS, audio_samples, check_sampling, make_sampler, override_sampler,
+                                      sampler_key, vits_frames)
     from genie_tts_amd.inference import tts_client
     from genie_tts_amd.model_manager import model_manager
     from genie_tts_amd.text_splitter import TextSplitter
@@ -126,9 +128,17 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
         except (TypeError, ValueError) as e:
             reply(kind="error", id=msg["id"], detail=f"sampling: {e}")
             return
+        out_rate = msg.get("sample_rate")   # None: 32 kHz, converted to PCM on the host as ever
+        try:                          # likewise an output rate the engine's output stage does not have
+            if out_rate is not None:
+                audio_samples(0, out_rate)
+                out_rate = int(out_rate)
+        except (TypeError, ValueError) as e:
+            reply(kind="error", id=msg["id"], detail=f"sample_rate: {e}")
+            return
         r = {"id": msg["id"], "character_name": msg["character_name"], "sentences": sents, "next": 0,
              "force_steps": int(msg.get("force_steps") or 0), "save_path": msg.get("save_path"),
-             "chunks": [], "speed": speed, "sampling": sampling, "sampler": None}
+             "chunks": [], "speed": speed, "sampling": sampling, "sampler": None, "sample_rate": out_rate}
         resolve_sampler(r, model_manager.get(r["character_name"]))
         pending.append(r)
 
@@ -160,14 +170,23 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
         for r, i, wav in zip(group, idx, wavs):
             if r not in pending:      # failed or stopped meanwhile
                 continue
-            reply(kind="chunk", id=r["id"], data=A.to_pcm16(wav))
-            r["chunks"].append(np.asarray(wav, np.float32).reshape(-1))
+            if r["sample_rate"] is not None:   # int16 at the request's rate, as the GPU wrote it
+                wav = np.ascontiguousarray(wav, np.int16).reshape(-1)
+                reply(kind="chunk", id=r["id"], data=wav.tobytes())
+                r["chunks"].append(wav)
+            else:
+                reply(kind="chunk", id=r["id"], data=A.to_pcm16(wav))
+                r["chunks"].append(np.asarray(wav, np.float32).reshape(-1))
             r["done"] = i + 1
             if r["done"] == len(r["sentences"]):
                 pending.remove(r)
                 if r["save_path"]:
                     try:              # a client-supplied path: its failure ends this request only
-                        A.write_wav(r["save_path"], np.concatenate(r["chunks"]))
+                        if r["sample_rate"] is not None:   # the streamed samples, the header at their rate
+                            api._write_pcm16_wav(r["save_path"], np.concatenate(r["chunks"]).tobytes(),
+                                                 r["sample_rate"])
+                        else:
+                            A.write_wav(r["save_path"], np.concatenate(r["chunks"]))
                     except Exception as e:   # noqa: BLE001
                         reply(kind="error", id=r["id"], detail=f"save_path: {type(e).__name__}: {e}")
                         continue
@@ -228,6 +247,9 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
             overlapped = pipeline and eng is not None
             speeds = [r["speed"] for r in group]
             rate = {} if all(v == 1.0 for v in speeds) else {"speed": speeds}
+            out_rates = [r["sample_rate"] for r in group]
+            if any(v is not None for v in out_rates):   # a round mixes rates: each item its own, as int16
+                rate.update(sample_rate=out_rates, pcm16=[v is not None for v in out_rates])
             wavs = tts_client.tts_batch_vocoder(items, toks, ref, m, overlapped=overlapped, **rate)
         except Exception as e:       # noqa: BLE001
             finish_inflight()
@@ -471,6 +493,9 @@ def create_app(router: Router):
         temperature: Optional[float] = Field(None, gt=0.0)
         repetition_penalty: Optional[float] = Field(None, gt=0.0)
         seed: Optional[int] = Field(None, ge=0, lt=1 << 64)
+        # output sample rate: the stream is then the GPU's int16 samples at that rate (header
+        # X-Sample-Rate); absent: 32 kHz, converted on the host as ever
+        sample_rate: Optional[Literal[8000, 16000, 22050, 24000, 32000, 44100, 48000]] = None
 
     def check(res: List[dict]) -> None:
         bad = [r for r in res if r["kind"] == "error"]
@@ -507,13 +532,15 @@ def create_app(router: Router):
                          **{k: v for k, v in (("top_k", payload.top_k), ("top_p", payload.top_p),
                                               ("temperature", payload.temperature),
                                               ("repetition_penalty", payload.repetition_penalty),
-                                              ("seed", payload.seed)) if v is not None})
+                                              ("seed", payload.seed), ("sample_rate", payload.sample_rate))
+                            if v is not None})
         try:    # surface "not found" as 404 before the stream starts, as the reference does
             first = await gen.__anext__()
         except StopAsyncIteration:
             first = None
         except RuntimeError as e:
-            code = 404 if "not found" in str(e) else 400 if str(e).startswith(("speed:", "sampling:")) else 500
+            code = (404 if "not found" in str(e) else
+                    400 if str(e).startswith(("speed:", "sampling:", "sample_rate:")) else 500)
             raise HTTPException(status_code=code, detail=str(e))
 
         async def body():
@@ -521,7 +548,8 @@ def create_app(router: Router):
                 yield first
                 async for c in gen:
                     yield c
-        return StreamingResponse(body(), media_type="audio/wav")
+        headers = None if payload.sample_rate is None else {"X-Sample-Rate": str(payload.sample_rate)}
+        return StreamingResponse(body(), media_type="audio/wav", headers=headers)
 
     @app.post("/stop")
     async def stop_endpoint():

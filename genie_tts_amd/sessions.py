@@ -177,7 +177,11 @@ class VitsSession(_Session):
     Speech rate: an optional "speed" feed entry (a scalar, 0.25 .. 4, default 1; the graph was
     exported with it fixed at 1) resamples the latent to T' = engine.vits_frames(G, speed) frames
     before enc_p.proj, so the audio is 640 T' samples at unchanged pitch.  eps_fn is then called
-    as `eps_fn(G, T') -> [192, T']`."""
+    as `eps_fn(G, T') -> [192, T']`.
+
+    Output format: optional "sample_rate" (one of engine.SAMPLE_RATES) and "pcm16" feed entries
+    run the engine's output stage behind the vocoder (Engine.audio_convert): the audio is then
+    engine.audio_samples(640 T', sample_rate) samples, float32 or int16."""
     OUTPUTS = (NodeArg("audio", ("1280*G",), "tensor(float)"),)
 
     def __init__(self, engine, version: str, noise_scale: float = 0.5, eps_fn=None, noise: str = "philox",
@@ -241,8 +245,9 @@ class VitsSession(_Session):
         else:
             self._need(f, "ge", "ge_advanced")
             cond = dict(ge=f["ge"], ge_advanced=f["ge_advanced"])
+        fmt = {k: f[k] for k in ("sample_rate", "pcm16") if f.get(k) is not None}   # none given: today's call
         audio = self.engine.vits_decode(f["text_seq"], sem, eps=eps, noise_scale=self.noise_scale, noise_seed=seed,
-                                        speed=speed, **cond)
+                                        speed=speed, **cond, **fmt)
         return self._select(output_names, {"audio": _np(audio)})
 
 

@@ -247,7 +247,36 @@ int gsv_vits_decode(gsv_engine* eng, const int64_t* text_seq, int32_t n_text,
  *   eps is [192, T'] then, and the Philox counter is the element index over 192 * T'.
  * In a batch every item has its own speed.  The segmented generator pass lays the
  * utterances out by T'_i; the packed front ("seg_front") is used only when every item's
- * T' equals its T, otherwise the fronts run per item on the lanes. */
+ * T' equals its T, otherwise the fronts run per item on the lanes.
+ *
+ * Output format (`out_rate`, `out_format`, `out`; the reference delivers 16-bit PCM chunks at
+ * 32 kHz, and a caller who needs another rate resamples on the host).  The engine's audio is
+ * 32 kHz float32; the output stage converts it on the GPU in one launch.
+ *   Rates: out_rate in {8000, 16000, 22050, 24000, 32000, 44100, 48000}; 0 means 32000; anything
+ *   else is GSV_E_ARG.  g = gcd(32000, out_rate), up = out_rate / g, down = 32000 / g
+ *   (1/4, 1/2, 441/640, 3/4, 1/1, 441/320, 3/2).
+ *   Length: n_out = gsv_audio_samples(n_in, out_rate) = ceil(n_in * up / down) in integers, the
+ *   one place it is computed.
+ *   Filter (scipy.signal.resample_poly's default, restated): m = max(up, down), half = 10 m,
+ *   2 half + 1 taps, h[i] = (1/m) sinc((i - half) / m) I0(5 sqrt(1 - ((i - half) / half)^2)) / I0(5),
+ *   sinc(t) = sin(pi t) / (pi t), I0 by its power series, all in double; h is normalised to sum 1,
+ *   multiplied by up and rounded once to float32.
+ *   Resample: y[k] = sum_n h[k * down + half - n * up] * x[n] over 0 <= n < n_in with the h index
+ *   inside [0, 2 half]: zeros outside the signal, no edge extension.  Each y[k] is ONE float32
+ *   chain over ascending n (acc = 0; acc = fmaf(h, x[n], acc)); terms whose coefficient or sample
+ *   is a padding zero may be included.  No split sums, no order that depends on a tile: every
+ *   entry point gives the same bits for the same input.  out_rate 32000 is a plain copy.
+ *   Format: out_format 0 is float32 y; 1 is signed 16-bit,
+ *   (int16) trunc(min(max(y * 32767.0f, -32768.0f), 32767.0f)) -- the reference's
+ *   (x * 32767).astype(int16) with saturation (the vocoder's tanh stays within 1; the resampled
+ *   signal can overshoot).  Another out_format is GSV_E_ARG.
+ * In an item: `audio` (32 kHz float32) is still required and written; when `out` is non-NULL the
+ * stage also writes out[gsv_audio_samples(640 * gsv_vits_frames(n_sem, speed), out_rate)] (float32
+ * or int16 elements) from the item's final audio -- after an fp16-range re-run, from the re-run's.
+ * A zero-initialised tail (out NULL) means "as before", and the two fields are then ignored; with
+ * `out`, a bad rate or format is GSV_E_ARG before any launch.  Every vocoder entry point that
+ * takes items honours the fields; a batch is one stage launch, each item its own rate and
+ * format; under gsv_vits_decode_async the stage runs on the vocoder's stream. */
 typedef struct {
     const int64_t* text_seq; int32_t n_text;   /* device */
     const int64_t* sem;      int32_t n_sem;    /* device */
@@ -259,8 +288,18 @@ typedef struct {
     int32_t noise_mode;
     float* audio;                              /* device [640 * gsv_vits_frames(n_sem, speed)] */
     float speed;                               /* speech rate, 0 == 1.0 (see above) */
+    int32_t out_rate;                          /* output stage: sample rate of `out`, 0 == 32000 */
+    int32_t out_format;                        /* 0: float32, 1: int16 */
+    void* out;                                 /* device [gsv_audio_samples(..)] or NULL: no stage */
 } gsv_vits_item;
 int gsv_vits_frames(int32_t n_sem, float speed);
+/* Samples of n_in 32 kHz samples at out_rate (see above); GSV_E_ARG for an unsupported rate or a
+ * negative n_in.  Pure: needs no device. */
+int gsv_audio_samples(int32_t n_in, int32_t out_rate);
+/* The output stage alone: audio_32k (device f32 [n_in]) -> out (device, float32 or int16
+ * [gsv_audio_samples(n_in, out_rate)]), stream-ordered like every other call. */
+int gsv_audio_convert(gsv_engine* eng, const float* audio_32k, int32_t n_in, int32_t out_rate,
+                      int32_t out_format, void* out, void* stream);
 /* One utterance, synchronously, as gsv_vits_decode but described by an item (so with its
  * speed and noise_mode 2).  Bit-identical to gsv_vits_decode for speed 0 or 1 and
  * noise_mode 0 or 1. */
