@@ -177,11 +177,13 @@ GemmArgs gemm_w16(int M, int N, int K, const float* A, long lda, const W16& W, c
 
 void layernorm_rows_d(const float* in, float* out, int rows, int D, const float* g, const float* b, float eps,
                       hipStream_t s) {
+    if (rows <= 0) return;
     hipLaunchKernelGGL(k_ln_rows_d, dim3(rows), dim3(256), 0, s, in, out, D, g, b, eps, 0, 0L, nullptr, nullptr);
 }
 
 void layernorm_rows_d_slabs(const float* slabs, int nslab, long slab_stride, const float* bias, const float* res,
                             float* out, int rows, int D, const float* g, const float* b, float eps, hipStream_t s) {
+    if (rows <= 0) return;
     hipLaunchKernelGGL(k_ln_rows_d, dim3(rows), dim3(256), 0, s, slabs, out, D, g, b, eps, nslab, slab_stride, bias,
                        res);
 }

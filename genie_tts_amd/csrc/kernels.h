@@ -67,6 +67,23 @@ struct GemmArgs {
     int cus, small_ns;
 };
 void gemm_nt(const GemmArgs& a, hipStream_t s);
+// The kernel gemm_nt launches for `a` (the one statement of its dispatch rule; host only, no HIP
+// call).  Negative: an argument set gemm_nt refuses (it aborts with a message).
+enum GemmForm {
+    GF_BAD_SMALL_NS = -3,    // small-M ring depth (GemmArgs::small_ns) not 0 / 2 / 3 / 4
+    GF_BAD_PRESPLIT = -2,    // Ah on a shape without the large-M path
+    GF_BAD_SPLITW = -1,      // Wl with an unsupported shape, an A prologue or EPI_VQDIST
+    GF_GENERIC_F32 = 0,      // k_gemm_nt<false>
+    GF_GENERIC_F16 = 1,      // k_gemm_nt<true>
+    GF_X2 = 2,               // k_gemm_x2
+    GF_SMALLM2 = 3,          // k_gemm_x3 SmallM, ring of 2 / 3 / 4 stages
+    GF_SMALLM3 = 4,
+    GF_SMALLM4 = 5,
+    GF_LARGEM = 6,           // k_gemm_x3 LargeM
+    GF_LARGEM_PS = 7,        // ... its pre-split-A twin
+    GF_SPLITW = 8,           // k_gemm_x3 SplitW
+};
+GemmForm gemm_form(const GemmArgs& a);
 // Args of a GEMM with fp16 weights W[N][K] (ldw = K): C = epi(A W^T + bias)
 GemmArgs gemm_f16(int M, int N, int K, const float* A, long lda, const void* W, const float* bias, float* C,
                   long ldc, int mode, const float* res = nullptr, long ldr = 0);

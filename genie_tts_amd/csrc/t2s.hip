@@ -465,36 +465,12 @@ __global__ __launch_bounds__(64 * (BM / 32) * (BN / 32 / WTN)) void k_gemm_x3(Ge
 //     blocks) lie between and are kept for option gemm_small_ns only; the XCD remap changed
 //     nothing (profiles/vstream_chain_gemm_forms.txt).  The ring depth changes neither the MFMA
 //     sequence nor the K partition (equal hashes there).
-enum class X3Form { SplitW, LargeM, SmallM };
 
 // Ring depth of the small-M form for `blocks` workgroups: two stages when the caller names the CUs
 // of its stream (a.cus) and the grid exceeds them, else four; a.small_ns forces it.
 static int small_m_stages(const GemmArgs& a, long blocks) {
     if (a.small_ns) return a.small_ns;
     return a.cus > 0 && blocks > a.cus ? 2 : 4;
-}
-
-static void launch_x3(const GemmArgs& a, int z, hipStream_t s, X3Form form) {
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((a.N + 63) / 64, (a.M + 63) / 64, z), dim3(256), 0, s, a);
-    };
-    switch (form) {
-        case X3Form::SplitW: go(k_gemm_x3<64, 64, 2, true, 1, true>); break;
-        case X3Form::LargeM:
-            if (a.Ah) go(k_gemm_x3<64, 64, 2, false, 1, true, true>);
-            else go(k_gemm_x3<64, 64, 2, false, 1, true>);
-            break;
-        case X3Form::SmallM:
-            switch (small_m_stages(a, (long)((a.N + 63) / 64) * ((a.M + 63) / 64) * z)) {
-                case 2: go(k_gemm_x3<64, 64, 2>); break;
-                case 3: go(k_gemm_x3<64, 64, 3>); break;
-                case 4: go(k_gemm_x3<64, 64, 4>); break;
-                default:
-                    std::fprintf(stderr, "gemm_nt: small-M ring depth %d\n", a.small_ns);
-                    std::abort();
-            }
-            break;
-    }
 }
 
 static bool gemm_big(const GemmArgs& a) { return (long)((a.M + 63) / 64) * ((a.N + 63) / 64) >= 1024; }
@@ -510,40 +486,61 @@ bool gemm_presplit_path(int M, int N, int K, long lda) {
 
 bool gemm_slabs_supported(int K, long lda, long ldw) { return K % GX_KS == 0 && lda % 4 == 0 && ldw % 8 == 0; }
 
-void gemm_nt(const GemmArgs& a, hipStream_t s) {
-    dim3 grid((a.N + 63) / 64, (a.M + 63) / 64);
+// grid.z of the fp16-weight kernels: the K slices of EPI_SLAB
+static int gemm_z(const GemmArgs& a) { return a.mode == EPI_SLAB ? a.ksplit : 1; }
+
+GemmForm gemm_form(const GemmArgs& a) {
     if (a.Wl) {
         // split fp32 weights run only on k_gemm_x3 (every M: its partition does not depend
         // on M, so packed and per-sentence rows stay identical); the loaders check the shapes
-        if (!gemm_w16_supported(a.K, a.lda, a.ldw) || a.a_nslab != 0 || a.mode == EPI_VQDIST) {
-            std::fprintf(stderr, "gemm_nt: split-weight GEMM with unsupported shape K=%d lda=%ld\n", a.K, a.lda);
-            std::abort();
-        }
-        launch_x3(a, a.mode == EPI_SLAB ? a.ksplit : 1, s, X3Form::SplitW);
-        return;
+        if (!gemm_w16_supported(a.K, a.lda, a.ldw) || a.a_nslab != 0 || a.mode == EPI_VQDIST) return GF_BAD_SPLITW;
+        return GF_SPLITW;
     }
     // fp16 weights -> split-activation f16 MFMA; the VQ distance GEMM stays on the
     // exact f32 path (its argmin must see the f32 dot products).
     if (a.w_f16 && a.mode != EPI_VQDIST && a.K % GX_KS == 0 && a.lda % 4 == 0 && a.ldw % 8 == 0) {
-        if (a.mode == EPI_SLAB) grid.z = a.ksplit;
+        if (a.Ah && !gemm_presplit_path(a.M, a.N, a.K, a.lda)) return GF_BAD_PRESPLIT;   // the caller asked gemm_presplit_path
         // the LDS-DMA pipeline reads A as stored: a slab-summing A prologue stays on k_gemm_x2
         // (M > 512: the register-staged kernel's 128-k steps win once the grid covers the chip)
-        if (a.Ah && !gemm_presplit_path(a.M, a.N, a.K, a.lda)) {   // the caller asked gemm_presplit_path
+        if (a.a_nslab == 0 && gemm_big(a)) return a.Ah ? GF_LARGEM_PS : GF_LARGEM;
+        if (a.a_nslab == 0 && a.M <= 512) {
+            switch (small_m_stages(a, (long)((a.N + 63) / 64) * ((a.M + 63) / 64) * gemm_z(a))) {
+                case 2: return GF_SMALLM2;
+                case 3: return GF_SMALLM3;
+                case 4: return GF_SMALLM4;
+                default: return GF_BAD_SMALL_NS;
+            }
+        }
+        return GF_X2;
+    }
+    return a.w_f16 ? GF_GENERIC_F16 : GF_GENERIC_F32;
+}
+
+void gemm_nt(const GemmArgs& a, hipStream_t s) {
+    const GemmForm form = gemm_form(a);
+    const bool mfma16 = form >= GF_X2;   // the fp16-weight kernels split K over grid.z; the generic ones have no EPI_SLAB
+    const dim3 grid((a.N + 63) / 64, (a.M + 63) / 64, mfma16 ? gemm_z(a) : 1);
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, a); };
+    switch (form) {
+        case GF_BAD_SPLITW:
+            std::fprintf(stderr, "gemm_nt: split-weight GEMM with unsupported shape K=%d lda=%ld\n", a.K, a.lda);
+            std::abort();
+        case GF_BAD_PRESPLIT:
             std::fprintf(stderr, "gemm_nt: pre-split A on a shape without the large-M path (M=%d N=%d)\n", a.M, a.N);
             std::abort();
-        }
-        if (a.a_nslab == 0 && gemm_big(a))
-            launch_x3(a, grid.z, s, X3Form::LargeM);
-        else if (a.a_nslab == 0 && a.M <= 512)
-            launch_x3(a, grid.z, s, X3Form::SmallM);
-        else
-            hipLaunchKernelGGL(k_gemm_x2, grid, dim3(256), 0, s, a);
-        return;
+        case GF_BAD_SMALL_NS:
+            std::fprintf(stderr, "gemm_nt: small-M ring depth %d\n", a.small_ns);
+            std::abort();
+        case GF_GENERIC_F32: go(k_gemm_nt<false>); break;
+        case GF_GENERIC_F16: go(k_gemm_nt<true>); break;
+        case GF_X2: go(k_gemm_x2); break;
+        case GF_SMALLM2: go(k_gemm_x3<64, 64, 2>); break;
+        case GF_SMALLM3: go(k_gemm_x3<64, 64, 3>); break;
+        case GF_SMALLM4: go(k_gemm_x3<64, 64, 4>); break;
+        case GF_LARGEM: go(k_gemm_x3<64, 64, 2, false, 1, true>); break;
+        case GF_LARGEM_PS: go(k_gemm_x3<64, 64, 2, false, 1, true, true>); break;
+        case GF_SPLITW: go(k_gemm_x3<64, 64, 2, true, 1, true>); break;
     }
-    if (a.w_f16)
-        hipLaunchKernelGGL(k_gemm_nt<true>, grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL(k_gemm_nt<false>, grid, dim3(256), 0, s, a);
 }
 
 // =====================================================================

@@ -148,6 +148,42 @@ def make_sampler(top_k: int = 15, temperature: float = 1.0, repetition_penalty: 
     return Sampler(top_k, temperature, repetition_penalty, int(greedy), seed, max_steps, force_steps, float(top_p))
 
 
+class GemmDesc(ctypes.Structure):
+    """gsv_gemm_desc (include/genie_engine.h): one gemm_nt launch, flat."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("M", "N", "K", "w_kind", "mode", "dry")] + [
+        ("a", ctypes.c_void_p), ("lda", ctypes.c_int64),
+        ("w", ctypes.c_void_p), ("wl", ctypes.c_void_p), ("ldw", ctypes.c_int64),
+        ("bias", ctypes.c_void_p),
+        ("c", ctypes.c_void_p), ("ldc", ctypes.c_int64),
+        ("res", ctypes.c_void_p), ("ldr", ctypes.c_int64),
+        ("rowsq", ctypes.c_void_p), ("colsq", ctypes.c_void_p),
+        ("kv_k", ctypes.c_void_p), ("kv_v", ctypes.c_void_p), ("kv_tmax", ctypes.c_int32), ("kv_pos0", ctypes.c_int32),
+        ("kv_row_pos", ctypes.c_void_p), ("kv_seq_stride", ctypes.c_int64), ("kv_row_seq", ctypes.c_void_p),
+        ("kv_row_skip", ctypes.c_void_p),
+        ("ksplit", ctypes.c_int32), ("a_nslab", ctypes.c_int32), ("slab_stride", ctypes.c_int64),
+        ("a_slab_stride", ctypes.c_int64),
+        ("a_bias", ctypes.c_void_p), ("a_relu", ctypes.c_int32), ("cus", ctypes.c_int32),
+        ("ah", ctypes.c_void_p), ("al", ctypes.c_void_p), ("ch", ctypes.c_void_p), ("cl", ctypes.c_void_p),
+        ("small_ns", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class RowsDesc(ctypes.Structure):
+    """gsv_rows_desc (include/genie_engine.h): one row-kernel launch."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("op", "rows", "D", "nslab")] + [
+        ("in_", ctypes.c_void_p), ("out", ctypes.c_void_p), ("ld", ctypes.c_int64), ("slab_stride", ctypes.c_int64),
+        ("g", ctypes.c_void_p), ("b", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("res", ctypes.c_void_p),
+        ("out_hi", ctypes.c_void_p), ("out_lo", ctypes.c_void_p),
+        ("eps", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+# gsv_debug_gemm's modes (EpiMode, csrc/kernels.h) and the forms it reports (GemmForm)
+EPI = {"store": 0, "relu": 1, "resid": 2, "qkv": 3, "vqdist": 4, "mish": 5, "slab": 6, "gelu": 7, "relu_split": 8}
+GEMM_FORMS = ("generic_f32", "generic_f16", "x2", "small_m2", "small_m3", "small_m4", "large_m", "large_m_ps",
+              "split_w")
+ROW_OPS = {"layernorm_rows": 0, "layernorm_rows_slabs": 1, "layernorm_rows_d": 2, "layernorm_rows_d_slabs": 3,
+           "sumsq_rows": 4, "argmin_dist_rows": 5}
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -222,6 +258,8 @@ def lib():
         L.gsv_f16_exact.argtypes = [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
         L.gsv_request_stop.argtypes = [vp, ctypes.c_int32]
         L.gsv_debug_hbm_copy.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_float)]
+        L.gsv_debug_gemm.argtypes = [ctypes.POINTER(GemmDesc), vp, ctypes.POINTER(ctypes.c_int32)]
+        L.gsv_debug_rows.argtypes = [ctypes.POINTER(RowsDesc), vp]
         _lib = L
     return _lib
 
@@ -239,7 +277,7 @@ EXPORTED = (
     "gsv_vits_decode_batch_async", "gsv_vits_batch_wait", "gsv_ref_encode", "gsv_roberta_batch",
     "gsv_f16_exact", "gsv_request_stop", "gsv_debug_hbm_copy", "gsv_vits_frames", "gsv_vits_decode_item",
     "gsv_debug_interp_linear", "gsv_t2s_generate_each", "gsv_debug_sample_each",
-    "gsv_audio_samples", "gsv_audio_convert",
+    "gsv_audio_samples", "gsv_audio_convert", "gsv_debug_gemm", "gsv_debug_rows",
 )
 
 
@@ -362,6 +400,47 @@ def debug_conv1d_h(x, v, scale, bias=None, dil=1, pad=0, in_act=False, slope=0.1
                                     tout, int(in_act), ctypes.c_float(slope), _ptr(ovf), _stream()),
            "gsv_debug_conv1d_h")
     return out, int(ovf.item())
+
+
+def gemm_desc(M, N, K, *, w_kind=1, mode="store", dry=False, **f) -> GemmDesc:
+    """A GemmDesc from sizes and fields; a field is an int, None, or anything with data_ptr()."""
+    d = GemmDesc()
+    d.M, d.N, d.K, d.w_kind, d.mode, d.dry = M, N, K, w_kind, EPI[mode] if isinstance(mode, str) else mode, int(dry)
+    for k, v in f.items():
+        if not hasattr(d, k):
+            raise TypeError(f"gsv_gemm_desc has no field {k}")
+        setattr(d, k, v.data_ptr() if hasattr(v, "data_ptr") else v)
+    return d
+
+
+def debug_gemm_form(M, N, K, **f) -> str:
+    """The kernel gemm_nt would launch (a name of GEMM_FORMS), from the hook's dry path: no HIP
+    call, so the pointers may be any aligned non-zero integers.  EngineError for a refused set."""
+    form = ctypes.c_int32(-1)
+    _check(lib().gsv_debug_gemm(ctypes.byref(gemm_desc(M, N, K, dry=True, **f)), None, ctypes.byref(form)),
+           "gsv_debug_gemm")
+    return GEMM_FORMS[form.value]
+
+
+def debug_gemm(M, N, K, **f) -> str:
+    """Run gemm_nt once on cuda tensors (tests; the fields of gsv_gemm_desc by name: a, lda, w, wl,
+    ldw, bias, c, ldc, mode, ...) on the current stream; returns the form that ran."""
+    form = ctypes.c_int32(-1)
+    _check(lib().gsv_debug_gemm(ctypes.byref(gemm_desc(M, N, K, **f)), _stream(), ctypes.byref(form)),
+           "gsv_debug_gemm")
+    return GEMM_FORMS[form.value]
+
+
+def debug_rows(op: str, rows: int, D: int, inp, out, **f):
+    """Run one row kernel (a name of ROW_OPS) on cuda tensors; fields of gsv_rows_desc by name."""
+    d = RowsDesc()
+    d.op, d.rows, d.D = ROW_OPS[op], rows, D
+    d.in_, d.out = inp.data_ptr(), out.data_ptr()
+    for k, v in f.items():
+        if not hasattr(d, k):
+            raise TypeError(f"gsv_rows_desc has no field {k}")
+        setattr(d, k, v.data_ptr() if hasattr(v, "data_ptr") else v)
+    _check(lib().gsv_debug_rows(ctypes.byref(d), _stream() if rows > 0 else None), "gsv_debug_rows")
 
 
 def debug_sample(logits, seen, sampler: "Sampler", step: int):

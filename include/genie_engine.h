@@ -461,6 +461,57 @@ int gsv_debug_sample(const float* logits, const uint32_t* seen, int B, const gsv
 int gsv_debug_sample_each(const float* logits, const uint32_t* seen, int B, const gsv_sampler* samplers,
                           const int32_t* streams, int step, int64_t* tokens, uint8_t* stop, void* stream);
 
+/* One launch of the engine's GEMM entry (gemm_nt, csrc/t2s.hip) on device buffers, engine-free:
+ * C(m,n) = epi(sum_k A[m lda + k] W[n ldw + k] + bias[n]).  Every pointer is a device pointer, 0
+ * where the launch has none.
+ *   w_kind: 0 f32 weights in w; 1 fp16 weights in w; 2 split fp32 weights, fp16 hi plane in w and
+ *     lo plane in wl (lo = fp16((w - hi) 2^11)).
+ *   mode: 0 store, 1 relu, 2 res + v, 3 q columns + K/V-cache scatter (kv_*), 4 VQ distance
+ *     (rowsq, colsq), 5 mish, 6 split-K slabs (ksplit, slab_stride; no bias), 7 gelu, 8 relu as fp16
+ *     hi / lo planes (ch, cl; no c).
+ *   a_nslab > 0: A = relu?(a_bias + the sum of a_nslab slabs a_slab_stride apart).  ah / al: A's fp16
+ *     hi / lo planes (large-M form only).  cus / small_ns: the stream's CUs and a forced small-M ring
+ *     depth (0, 2, 3, 4), host only.
+ *   dry != 0: check the arguments and report the form, launch nothing (no HIP call).
+ * *form = the kernel that ran (or would): 0 generic f32, 1 generic f16, 2 x2, 3 / 4 / 5 small-M with
+ * 2 / 3 / 4 stages, 6 large-M, 7 large-M with pre-split A, 8 split weights.
+ * GSV_E_ARG, before any HIP call, for an argument set the kernels' loads and stores do not cover:
+ * null or misaligned pointers, K % 32, leading dimensions, a mode on a path that has no such
+ * epilogue (gsv_last_error names it). */
+typedef struct gsv_gemm_desc {
+    int32_t M, N, K, w_kind, mode, dry;
+    const float* a; int64_t lda;
+    const void* w; const void* wl; int64_t ldw;
+    const float* bias;
+    float* c; int64_t ldc;
+    const float* res; int64_t ldr;
+    const float* rowsq; const float* colsq;
+    float* kv_k; float* kv_v; int32_t kv_tmax, kv_pos0;
+    const int32_t* kv_row_pos; int64_t kv_seq_stride; const int32_t* kv_row_seq; const uint8_t* kv_row_skip;
+    int32_t ksplit, a_nslab; int64_t slab_stride, a_slab_stride;
+    const float* a_bias; int32_t a_relu, cus;
+    const void* ah; const void* al; void* ch; void* cl;
+    int32_t small_ns, reserved;
+} gsv_gemm_desc;
+int gsv_debug_gemm(const gsv_gemm_desc* d, void* stream, int32_t* form);
+/* One launch of a row kernel of csrc/t2s.hip / csrc/hubert.hip on device buffers.
+ *   op 0 layernorm_rows (D = 512, eps 1e-5): in -> out [rows][512] with g, b.
+ *   op 1 layernorm_rows_slabs: LayerNorm of res + (bias + sum of nslab slabs of `in`, slab_stride
+ *     apart); out_hi / out_lo (optional, both or neither) take the fp16 split of out.
+ *   op 2 layernorm_rows_d, op 3 layernorm_rows_d_slabs: the same over D <= 1024 with eps.
+ *   op 4 sumsq_rows: out[r] = sum_c in[r ld + c]^2, c < D.
+ *   op 5 argmin_dist_rows: out (int64 [rows]) = the first index of the least of in[r D + c], c < D.
+ * rows == 0 returns 0 without a launch; GSV_E_ARG before any HIP call for null pointers or sizes
+ * the kernel does not cover. */
+typedef struct gsv_rows_desc {
+    int32_t op, rows, D, nslab;
+    const float* in; void* out; int64_t ld, slab_stride;
+    const float* g; const float* b; const float* bias; const float* res;
+    void* out_hi; void* out_lo;
+    float eps; int32_t reserved;
+} gsv_rows_desc;
+int gsv_debug_rows(const gsv_rows_desc* d, void* stream);
+
 /* Probe: replay one kernel configuration `iters` times (hipGraph) between HIP
  * events on the engine stream; *us = average microseconds per launch.
  * which: 0/1 empty kernel (1/256 blocks), 2 QKV GEMV (+LN prologue), 3 QKV GEMV,
