@@ -72,6 +72,25 @@ struct ConvArgs {
     int ws;
 };
 void conv1d(const ConvArgs& a, hipStream_t s);
+// The kernel conv1d launches for `a`: a pure host function, the one rule conv1d, conv1d_deferred and
+// conv1d_h switch on (and the tests read through gsv_debug_conv's dry path).
+enum ConvPath {
+    CP_NONE = 0,        // not covered: no kernel instance (K), or a.wh on a shape the f16 path lacks
+    CP_F32 = 1,         // k_conv1d, one launch
+    CP_F32_SPLITK = 2,  // k_conv1d over grid.z = nsplit Cin slices + k_conv_reduce (or the deferred consumer)
+    CP_H = 3,           // k_conv_h (vits_convh.hip)
+    CP_WS = 4,          // k_conv_ws, the weight-stationary form
+};
+struct ConvForm {
+    int path;
+    int nsplit;   // f32: slabs (1: direct)
+    int v4;       // f32: the float4 weight loads (k_conv1d<KT, true>)
+    int chunk;    // f16: input channels per K-chunk, 32 or 8
+    int tile;     // f16: candidate 0..3 of the (WM, WN, KS) forms (2,2,1), (1,2,2), (1,1,4), (1,4,1)
+};
+ConvForm conv_form(const ConvArgs& a);
+// ... of the f16-split path alone (what conv1d_h runs; CP_NONE: it launches nothing)
+ConvForm conv_form_h(const ConvArgs& a);
 // conv1d that leaves a split-K conv unreduced: returns the slab count (>= 2) it left in a.part,
 // [nsplit][Cout][n_t] with conv1d's own nsplit and no reduce launched -- the next launch on the
 // stream sums them (ln_channels_slabs, wn_gate_slabs; a.out, a.mode and a.bias are then the
@@ -82,6 +101,8 @@ int conv1d_deferred(const ConvArgs& a, hipStream_t s);
 void seg_fill(int* seg, long n, const int* off, const int* len, int nseg, int f, hipStream_t s);
 // f16-split path; returns false (nothing launched) when the shape is not covered.
 bool conv1d_h(const ConvArgs& a, hipStream_t s);
+// the launch of a form conv_form_h gave for `a` (CP_H or CP_WS)
+void conv1d_h_launch(const ConvArgs& a, const ConvForm& f, hipStream_t s);
 
 // One ResBlock1 step of a narrow generator stage (C = 16 / 32) as one kernel (vits_mrf.hip):
 // xt = lrelu(conv1_d(lrelu(r)) + b1) in LDS only, then conv2 (kernel k, dilation 1) with e
@@ -96,6 +117,8 @@ struct MrfPairArgs {
     ConvArgs e;
 };
 bool mrf_pair(const MrfPairArgs& a, hipStream_t s);
+// nullptr when mrf_pair covers `a`, else the reason it does not (host only)
+const char* mrf_pair_why(const MrfPairArgs& a);
 
 // LayerNorm over channels per t: out = LN(x + y) (y may be null), eps 1e-5; seg (segmented
 // batch, as ConvArgs::seg): a gap column is written as zeros

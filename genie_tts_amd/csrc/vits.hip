@@ -170,9 +170,7 @@ __global__ __launch_bounds__(256) void k_conv_reduce(ConvArgs a, int nsplit) {
 }
 
 template <int KT>
-static void launch_conv(const ConvArgs& a, dim3 grid, hipStream_t s) {
-    const bool v4 = ((a.Cin * KT) % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.w) & 15) == 0) &&
-                    ((a.w_phase_stride % 4) == 0);
+static void launch_conv(const ConvArgs& a, dim3 grid, bool v4, hipStream_t s) {
     if (v4) hipLaunchKernelGGL((k_conv1d<KT, true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_conv1d<KT, false>), grid, dim3(256), 0, s, a);
 }
@@ -189,31 +187,48 @@ static int conv_ci(int K) {
     }
 }
 
+ConvForm conv_form(const ConvArgs& a) {
+    if (a.wh) {   // the f16-split path where it covers the shape, else the f32 kernel below
+        const ConvForm h = conv_form_h(a);
+        if (h.path != CP_NONE) return h;
+    }
+    ConvForm f{CP_NONE, 1, 0, 0, 0};
+    if (!(a.K == 1 || a.K == 2 || a.K == 3 || a.K == 4 || a.K == 5 || a.K == 7 || a.K == 11)) return f;
+    // Under-filled grids (the T=2G / S-frame encoder, MRTE and flow convs) split
+    // the Cin reduction so the launch covers the chip.
+    const int blocks = ((a.n_t + CONV_BN - 1) / CONV_BN) * ((a.Cout + CONV_BM - 1) / CONV_BM);
+    if (a.part && a.phases <= 1 && blocks < 128) {
+        const int nch = (a.Cin + conv_ci(a.K) - 1) / conv_ci(a.K);
+        f.nsplit = std::min(nch, (256 + blocks - 1) / blocks);
+        while (f.nsplit > 1 && (long)f.nsplit * a.Cout * a.n_t > a.part_cap) --f.nsplit;
+    }
+    f.path = f.nsplit > 1 ? CP_F32_SPLITK : CP_F32;
+    f.v4 = ((a.Cin * a.K) % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.w) & 15) == 0) &&
+           ((a.w_phase_stride % 4) == 0);
+    return f;
+}
+
 // defer: a conv that splits K leaves its slabs in a.part and launches no reduce.  Returns the
 // slab count (1: the conv wrote its own output).
 static int conv1d_run(const ConvArgs& a, hipStream_t s, bool defer) {
-    if (a.wh && conv1d_h(a, s)) return 1;
+    const ConvForm f = conv_form(a);
+    if (f.path == CP_H || f.path == CP_WS) {
+        conv1d_h_launch(a, f, s);
+        return 1;
+    }
+    if (f.path == CP_NONE) return 1;   // host validates K
     dim3 grid((a.n_t + CONV_BN - 1) / CONV_BN, (a.Cout + CONV_BM - 1) / CONV_BM,
               a.phases > 0 ? a.phases : 1);
-    // Under-filled grids (the T=2G / S-frame encoder, MRTE and flow convs) split
-    // the Cin reduction so the launch covers the chip.
-    int nsplit = 1;
-    const int blocks = (int)(grid.x * grid.y);
-    if (a.part && a.phases <= 1 && blocks < 128) {
-        const int nch = (a.Cin + conv_ci(a.K) - 1) / conv_ci(a.K);
-        nsplit = std::min(nch, (256 + blocks - 1) / blocks);
-        while (nsplit > 1 && (long)nsplit * a.Cout * a.n_t > a.part_cap) --nsplit;
-    }
+    const int nsplit = f.nsplit;
     if (nsplit > 1) grid.z = nsplit;
     switch (a.K) {
-        case 1: launch_conv<1>(a, grid, s); break;
-        case 2: launch_conv<2>(a, grid, s); break;
-        case 3: launch_conv<3>(a, grid, s); break;
-        case 4: launch_conv<4>(a, grid, s); break;
-        case 5: launch_conv<5>(a, grid, s); break;
-        case 7: launch_conv<7>(a, grid, s); break;
-        case 11: launch_conv<11>(a, grid, s); break;
-        default: return 1;   // host validates K
+        case 1: launch_conv<1>(a, grid, f.v4, s); break;
+        case 2: launch_conv<2>(a, grid, f.v4, s); break;
+        case 3: launch_conv<3>(a, grid, f.v4, s); break;
+        case 4: launch_conv<4>(a, grid, f.v4, s); break;
+        case 5: launch_conv<5>(a, grid, f.v4, s); break;
+        case 7: launch_conv<7>(a, grid, f.v4, s); break;
+        case 11: launch_conv<11>(a, grid, f.v4, s); break;
     }
     if (nsplit > 1 && !defer) {
         const long n = (long)a.Cout * a.n_t;
@@ -438,10 +453,11 @@ void ln_channels(const float* x, const float* y, float* out, int C, int T, const
                  const float* b, hipStream_t s, const int* seg) {
     if (C % 16 == 0 && C <= 256)
         hipLaunchKernelGGL(k_ln_channels_w, dim3((T + 3) / 4), dim3(64), 0, s, x, y, out, C, T, g, b, seg);
-    else if (!seg)
+    else if (!seg && C <= 4 * LNC_MAX)
         hipLaunchKernelGGL(k_ln_channels, dim3((T + 63) / 64), dim3(256), 0, s, x, y, out, C, T, g, b);
     else
-        std::abort();   // the segmented front's LayerNorms are all 192-channel
+        std::abort();   // the segmented front's LayerNorms are all 192-channel; k_ln_channels keeps
+                        // 4 x LNC_MAX channels and would leave the ones past them out
 }
 
 void ln_channels_slabs(const float* x, const float* slabs, int nsplit, const float* bias, float* out, int C, int T,

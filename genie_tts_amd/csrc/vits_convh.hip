@@ -449,73 +449,83 @@ void launch_ws(const ConvArgs& a, hipStream_t s) {
 // >= 2 tiles per lane.  The 3-tap convs stay on k_conv_h: there the per-tile staging and epilogue
 // outweigh the MFMAs and one block per CU hides them worse than k_conv_h's two (r06p: 549 / 389 us
 // against 417 / 328 at Cin 128 / 64).
-template <int KT>
-bool try_ws(const ConvArgs& a, hipStream_t s) {
-    if constexpr (KT == 7 || KT == 11) {
-        if (a.ws <= 0 || a.phases > 1 || a.o_tstride != 1 || a.o_toff != 0 || a.Cout % 64 != 0 ||
-            a.Cout != a.Cin ||
-            !(a.mode == CV_STORE || a.mode == CV_RESID || a.mode == CV_ACC_FIRST || a.mode == CV_ACC_ADD ||
-              a.mode == CV_ACC_MEAN))
-            return false;
-        if ((a.n_t + 255) / 256 < 2L * a.ws) return false;   // >= 2 tiles per lane
-        // only where k_conv_h would run its (2, 2, 1) form, whose MFMA sequence k_conv_ws runs: the
-        // same bits either way (a K-split form sums in another order)
-        if (convh_choice(a) != 0) return false;
-        if (a.Cin == 64) {
-            launch_ws<KT, 64>(a, s);
-            return true;
-        }
-        if constexpr (KT <= 7) {
-            if (a.Cin == 128) {
-                launch_ws<KT, 128>(a, s);
-                return true;
-            }
-        }
-    }
-    return false;
+static bool ws_covers(const ConvArgs& a, int tile) {
+    if (a.K != 7 && a.K != 11) return false;
+    if (a.ws <= 0 || a.phases > 1 || a.o_tstride != 1 || a.o_toff != 0 || a.Cout % 64 != 0 ||
+        a.Cout != a.Cin ||
+        !(a.mode == CV_STORE || a.mode == CV_RESID || a.mode == CV_ACC_FIRST || a.mode == CV_ACC_ADD ||
+          a.mode == CV_ACC_MEAN))
+        return false;
+    if ((a.n_t + 255) / 256 < 2L * a.ws) return false;   // >= 2 tiles per lane
+    // only where k_conv_h would run its (2, 2, 1) form, whose MFMA sequence k_conv_ws runs: the
+    // same bits either way (a K-split form sums in another order)
+    if (tile != 0) return false;
+    return a.Cin == 64 || (a.Cin == 128 && a.K == 7);
 }
 
 template <int KT, int CC>
-bool launch_h(const ConvArgs& a, hipStream_t s) {
-    const Cand* cands = convh_cands;
-    const int best = convh_choice(a);
-    const Cand c = cands[best];
+void launch_h(const ConvArgs& a, int tile, hipStream_t s) {
+    const Cand c = convh_cands[tile];
     const dim3 grid((a.n_t + 64 * c.wn - 1) / (64 * c.wn), (a.Cout + 32 * c.wm - 1) / (32 * c.wm),
                     a.phases > 1 ? a.phases : 1);
     if (c.wm == 2) hipLaunchKernelGGL((k_conv_h<KT, CC, 2, 2, 1>), grid, dim3(256), 0, s, a);
     else if (c.ks == 2) hipLaunchKernelGGL((k_conv_h<KT, CC, 1, 2, 2>), grid, dim3(256), 0, s, a);
     else if (c.ks == 4) hipLaunchKernelGGL((k_conv_h<KT, CC, 1, 1, 4>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_conv_h<KT, CC, 1, 4, 1>), grid, dim3(256), 0, s, a);
-    return true;
 }
 
 template <int KT>
-bool launch_kt(const ConvArgs& a, hipStream_t s) {
-    if (try_ws<KT>(a, s)) return true;
-    if (a.Cin % 32 == 0) return launch_h<KT, 32>(a, s);
-    if (a.Cin % 8 == 0) return launch_h<KT, 8>(a, s);
-    return false;
+void launch_kt(const ConvArgs& a, const ConvForm& f, hipStream_t s) {
+    if (f.path == CP_WS) {
+        if constexpr (KT == 7 || KT == 11) {
+            if (a.Cin == 64) launch_ws<KT, 64>(a, s);
+            else if constexpr (KT <= 7) launch_ws<KT, 128>(a, s);
+        }
+        return;
+    }
+    if (f.chunk == 32) launch_h<KT, 32>(a, f.tile, s);
+    else launch_h<KT, 8>(a, f.tile, s);
 }
 
 }  // namespace
 
-bool conv1d_h(const ConvArgs& a, hipStream_t s) {
-    if (!a.wh || !a.wscale || !a.ovf) return false;
+ConvForm conv_form_h(const ConvArgs& a) {
+    ConvForm f{CP_NONE, 1, 0, 0, 0};
+    if (!a.wh || !a.wscale || !a.ovf) return f;
     // a plain conv (one phase, unit output stride) or a ConvTranspose's polyphase form
     // (phases = output stride; dilation 1)
     const bool poly = a.phases > 1;
-    if (poly ? (a.o_tstride != a.phases || a.dil != 1) : a.o_tstride != 1) return false;
-    if (a.x_ts != 1 || a.dil < 1 || a.dil > DMAX) return false;
-    if ((reinterpret_cast<uintptr_t>(a.wh) & 15) != 0) return false;
-    switch (a.K) {
-        case 1: return launch_kt<1>(a, s);
-        case 2: return launch_kt<2>(a, s);
-        case 4: return launch_kt<4>(a, s);
-        case 3: return launch_kt<3>(a, s);
-        case 7: return launch_kt<7>(a, s);
-        case 11: return launch_kt<11>(a, s);
-        default: return false;
+    if (poly ? (a.o_tstride != a.phases || a.dil != 1) : a.o_tstride != 1) return f;
+    if (a.x_ts != 1 || a.dil < 1 || a.dil > DMAX) return f;
+    if ((reinterpret_cast<uintptr_t>(a.wh) & 15) != 0) return f;
+    if (!(a.K == 1 || a.K == 2 || a.K == 3 || a.K == 4 || a.K == 7 || a.K == 11)) return f;
+    const int tile = convh_choice(a);
+    if (ws_covers(a, tile)) {
+        f.path = CP_WS; f.chunk = 32; f.tile = 0;
+    } else if (a.Cin % 32 == 0) {
+        f.path = CP_H; f.chunk = 32; f.tile = tile;
+    } else if (a.Cin % 8 == 0) {
+        f.path = CP_H; f.chunk = 8; f.tile = tile;
     }
+    return f;
+}
+
+void conv1d_h_launch(const ConvArgs& a, const ConvForm& f, hipStream_t s) {
+    switch (a.K) {
+        case 1: launch_kt<1>(a, f, s); break;
+        case 2: launch_kt<2>(a, f, s); break;
+        case 4: launch_kt<4>(a, f, s); break;
+        case 3: launch_kt<3>(a, f, s); break;
+        case 7: launch_kt<7>(a, f, s); break;
+        case 11: launch_kt<11>(a, f, s); break;
+    }
+}
+
+bool conv1d_h(const ConvArgs& a, hipStream_t s) {
+    const ConvForm f = conv_form_h(a);
+    if (f.path == CP_NONE) return false;
+    conv1d_h_launch(a, f, s);
+    return true;
 }
 
 }  // namespace gsv

@@ -266,13 +266,21 @@ void launch(const MrfPairArgs& a, hipStream_t s) {
 
 }  // namespace
 
-bool mrf_pair(const MrfPairArgs& a, hipStream_t s) {
-    if (!a.w1 || !a.w2 || !a.s1 || !a.s2 || !a.ovf || a.dil < 1 || a.dil > DMAXM) return false;
+const char* mrf_pair_why(const MrfPairArgs& a) {
+    if (!a.w1 || !a.w2 || !a.s1 || !a.s2 || !a.b1 || !a.ovf) return "weights, scales, conv1's bias and the overflow flag are needed";
+    if (a.dil < 1 || a.dil > DMAXM) return "dilation outside 1 .. 5";
     if (a.e.o_tstride != 1 || a.e.o_toff != 0 || a.e.o_ts != 1 || a.e.o_cs != a.T || a.e.Cout != a.C ||
-        a.e.n_t != a.T || a.e.o_len != a.T || !a.e.bias || !a.e.res || a.e.r_cs != a.T || a.e.r_ts != 1)
-        return false;
+        a.e.n_t != a.T || a.e.o_len != a.T)
+        return "the output is [C][T], unit strides, every column";
+    if (!a.e.bias || !a.e.res || a.e.r_cs != a.T || a.e.r_ts != 1) return "conv2's bias and a [C][T] residual are needed";
     if (a.e.mode != CV_RESID && a.e.mode != CV_ACC_FIRST && a.e.mode != CV_ACC_ADD && a.e.mode != CV_ACC_MEAN)
-        return false;
+        return "modes RESID, ACC_FIRST, ACC_ADD and ACC_MEAN only";
+    if (!((a.K == 3 || a.K == 7 || a.K == 11) && (a.C == 16 || a.C == 32))) return "K in 3, 7, 11 and C in 16, 32 only";
+    return nullptr;
+}
+
+bool mrf_pair(const MrfPairArgs& a, hipStream_t s) {
+    if (mrf_pair_why(a)) return false;
     const int key = a.K * 100 + a.C;
     switch (key) {
         case 332: launch<3, 32>(a, s); return true;

@@ -176,6 +176,60 @@ class RowsDesc(ctypes.Structure):
         ("eps", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
+_I32, _I64, _F32, _VP = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
+
+
+class ConvDesc(ctypes.Structure):
+    """gsv_conv_desc (include/genie_engine.h): one conv1d launch, the fields of ConvArgs, flat."""
+    _fields_ = [(n, _I32) for n in ("Cin", "Tin", "Cout", "K", "dil", "pad", "n_t", "o_tstride", "o_toff", "o_len",
+                                    "in_act", "mode", "split", "phases", "tile_force", "ws", "dry", "deferred")] + [
+        ("in_slope", _F32), ("div", _F32),
+        ("x", _VP), ("x_cs", _I64), ("x_ts", _I64),
+        ("w", _VP), ("bias", _VP),
+        ("out", _VP), ("o_cs", _I64), ("o_ts", _I64),
+        ("res", _VP), ("r_cs", _I64), ("r_ts", _I64),
+        ("vec", _VP), ("acc", _VP), ("out2", _VP), ("res2", _VP),
+        ("w_phase_stride", _I64),
+        ("part", _VP), ("part_cap", _I64),
+        ("wh", _VP), ("wscale", _VP), ("ovf", _VP), ("wh_phase_stride", _I64), ("in_scale", _VP),
+        ("seg", _VP), ("vec_sstride", _I64)] + [
+        (n, _I64) for n in ("n_x", "n_w", "n_out", "n_res", "n_acc", "n_out2", "n_seg")]
+
+
+class MrfDesc(ctypes.Structure):
+    """gsv_mrf_desc: one mrf_pair launch."""
+    _fields_ = [(n, _I32) for n in ("T", "C", "K", "dil", "mode", "Cout", "n_t", "o_len", "o_tstride", "o_toff")] + [
+        ("div", _F32), ("reserved", _I32),
+        ("r", _VP), ("w1", _VP), ("s1", _VP), ("b1", _VP), ("w2", _VP), ("s2", _VP), ("bias2", _VP),
+        ("ovf", _VP), ("out", _VP), ("acc", _VP), ("seg", _VP)] + [
+        (n, _I64) for n in ("o_cs", "o_ts", "r_cs", "r_ts", "n_r", "n_out", "n_acc", "n_seg")]
+
+
+class MhaDesc(ctypes.Structure):
+    """gsv_mha_desc: one mha launch."""
+    _fields_ = [(n, _I32) for n in ("nq", "nk", "heads", "dk", "postdiv", "window")] + [
+        ("scale", _F32), ("reserved", _I32),
+        ("q", _VP), ("q_ts", _I64), ("q_cs", _I64),
+        ("k", _VP), ("k_ts", _I64), ("k_cs", _I64),
+        ("v", _VP), ("v_ts", _I64), ("v_cs", _I64),
+        ("out", _VP), ("o_ts", _I64), ("o_cs", _I64),
+        ("ek", _VP), ("ev", _VP), ("row_seg", _VP), ("row_seg_host", _VP)] + [
+        (n, _I64) for n in ("n_q", "n_k", "n_v", "n_out")]
+
+
+class VitsRowsDesc(ctypes.Structure):
+    """gsv_vits_rows_desc: one row kernel of csrc/vits.hip."""
+    _fields_ = [(n, _I32) for n in ("op", "C", "T", "nsplit", "nseg", "f")] + [
+        ("n", _I64), ("vec_sstride", _I64), ("div", _F32), ("reserved", _I32)] + [
+        (n, _VP) for n in ("x", "y", "z", "out", "g", "b", "bias", "vec", "seg", "off", "len")]
+
+
+# ConvMode (csrc/vits.h) and the paths gsv_debug_conv reports (ConvPath)
+CONV_MODES = {"store": 0, "relu": 1, "resid": 2, "vec": 3, "sub": 4, "tanh": 5, "acc_first": 6, "acc_add": 7,
+              "acc_mean": 8, "resid_vec": 9, "split_resid": 10}
+CONV_PATHS = ("none", "f32", "f32_splitk", "conv_h", "conv_ws")
+VITS_ROW_OPS = {"ln_channels": 0, "ln_channels_slabs": 1, "wn_gate": 2, "wn_gate_slabs": 3, "mean3": 4, "seg_fill": 5}
+
 # gsv_debug_gemm's modes (EpiMode, csrc/kernels.h) and the forms it reports (GemmForm)
 EPI = {"store": 0, "relu": 1, "resid": 2, "qkv": 3, "vqdist": 4, "mish": 5, "slab": 6, "gelu": 7, "relu_split": 8}
 GEMM_FORMS = ("generic_f32", "generic_f16", "x2", "small_m2", "small_m3", "small_m4", "large_m", "large_m_ps",
@@ -260,6 +314,10 @@ def lib():
         L.gsv_debug_hbm_copy.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_float)]
         L.gsv_debug_gemm.argtypes = [ctypes.POINTER(GemmDesc), vp, ctypes.POINTER(ctypes.c_int32)]
         L.gsv_debug_rows.argtypes = [ctypes.POINTER(RowsDesc), vp]
+        L.gsv_debug_conv.argtypes = [ctypes.POINTER(ConvDesc), vp, ctypes.POINTER(ctypes.c_int32)]
+        L.gsv_debug_mrf_pair.argtypes = [ctypes.POINTER(MrfDesc), vp]
+        L.gsv_debug_mha.argtypes = [ctypes.POINTER(MhaDesc), vp]
+        L.gsv_debug_vits_rows.argtypes = [ctypes.POINTER(VitsRowsDesc), vp]
         _lib = L
     return _lib
 
@@ -278,6 +336,7 @@ EXPORTED = (
     "gsv_f16_exact", "gsv_request_stop", "gsv_debug_hbm_copy", "gsv_vits_frames", "gsv_vits_decode_item",
     "gsv_debug_interp_linear", "gsv_t2s_generate_each", "gsv_debug_sample_each",
     "gsv_audio_samples", "gsv_audio_convert", "gsv_debug_gemm", "gsv_debug_rows",
+    "gsv_debug_conv", "gsv_debug_mrf_pair", "gsv_debug_mha", "gsv_debug_vits_rows",
 )
 
 
@@ -441,6 +500,82 @@ def debug_rows(op: str, rows: int, D: int, inp, out, **f):
             raise TypeError(f"gsv_rows_desc has no field {k}")
         setattr(d, k, v.data_ptr() if hasattr(v, "data_ptr") else v)
     _check(lib().gsv_debug_rows(ctypes.byref(d), _stream() if rows > 0 else None), "gsv_debug_rows")
+
+
+def _fill(d, fields, sizes=()):
+    """Set a desc's fields by name: an int / float, None, or a tensor (its data_ptr; for a name of
+    `sizes`, n_<name> = its element count unless given)."""
+    for k, v in fields.items():
+        if not hasattr(d, k):
+            raise TypeError(f"{type(d).__name__} has no field {k}")
+        if hasattr(v, "data_ptr"):
+            if k in sizes and "n_" + sizes[k] not in fields:
+                setattr(d, "n_" + sizes[k], v.numel())
+            v = v.data_ptr()
+        setattr(d, k, v)
+    return d
+
+
+_CONV_SIZES = {"x": "x", "w": "w", "wh": "w", "out": "out", "res": "res", "acc": "acc", "out2": "out2", "seg": "seg"}
+
+
+def conv_desc(*, mode="store", **f) -> ConvDesc:
+    """A ConvDesc from fields by name.  Defaults: dil 1, one phase, o_tstride 1, unit time strides,
+    in_slope 0.1, div 1; n_<buffer> from the tensors given; part_cap from part."""
+    d = ConvDesc()
+    d.dil = d.o_tstride = d.x_ts = d.o_ts = d.r_ts = d.phases = 1
+    d.in_slope, d.div = 0.1, 1.0
+    d.mode = CONV_MODES[mode] if isinstance(mode, str) else mode
+    if hasattr(f.get("part"), "numel") and "part_cap" not in f:
+        d.part_cap = f["part"].numel()
+    return _fill(d, f, _CONV_SIZES)
+
+
+def debug_conv(desc=None, stream=True, **f) -> dict:
+    """gsv_debug_conv on a ConvDesc (or the fields of conv_desc): one conv1d launch on the current
+    stream (stream = None: none is passed, for the dry path and the rejections, which make no HIP
+    call).  Returns the form: path (a name of CONV_PATHS) and nsplit, v4 (f32) or chunk, tile
+    (f16), and the slabs a deferred launch left."""
+    d = desc if desc is not None else conv_desc(**f)
+    form = (ctypes.c_int32 * 4)()
+    _check(lib().gsv_debug_conv(ctypes.byref(d), _stream() if stream and not d.dry else None, form), "gsv_debug_conv")
+    path = CONV_PATHS[form[0]]
+    if path in ("conv_h", "conv_ws"):
+        return {"path": path, "chunk": form[1], "tile": form[2], "slabs": form[3]}
+    return {"path": path, "nsplit": form[1], "v4": bool(form[2]), "slabs": form[3]}
+
+
+def debug_mrf_pair(stream=True, *, mode="resid", **f):
+    """gsv_debug_mrf_pair: one fused ResBlock step; T, C, K, dil and the tensors r, w1, s1, b1, w2,
+    s2, bias2, ovf, out / acc (seg) by name.  The epilogue's geometry defaults to mrf_pair's own."""
+    d = MrfDesc()
+    T, C = f["T"], f["C"]
+    d.Cout, d.n_t, d.o_len, d.o_tstride, d.o_toff = C, T, T, 1, 0
+    d.o_cs, d.o_ts, d.r_cs, d.r_ts, d.div = T, 1, T, 1, 1.0
+    d.mode = CONV_MODES[mode] if isinstance(mode, str) else mode
+    _fill(d, f, {"r": "r", "out": "out", "acc": "acc", "seg": "seg"})
+    _check(lib().gsv_debug_mrf_pair(ctypes.byref(d), _stream() if stream else None), "gsv_debug_mrf_pair")
+
+
+def debug_mha(stream=True, **f):
+    """gsv_debug_mha: one attention launch; the fields of gsv_mha_desc by name (row_seg_host: an
+    int32 numpy array, kept alive by the caller's reference for the call)."""
+    d = MhaDesc()
+    d.scale = 1.0
+    host = f.pop("row_seg_host", None)
+    if host is not None:
+        host = np.ascontiguousarray(host, np.int32)
+        d.row_seg_host = host.ctypes.data
+    _fill(d, f, {"q": "q", "k": "k", "v": "v", "out": "out"})
+    _check(lib().gsv_debug_mha(ctypes.byref(d), _stream() if stream else None), "gsv_debug_mha")
+
+
+def debug_vits_rows(op: str, stream=True, **f):
+    """gsv_debug_vits_rows: one row kernel of csrc/vits.hip (a name of VITS_ROW_OPS)."""
+    d = VitsRowsDesc()
+    d.op, d.div = VITS_ROW_OPS[op] if isinstance(op, str) else op, 1.0
+    _fill(d, f)
+    _check(lib().gsv_debug_vits_rows(ctypes.byref(d), _stream() if stream else None), "gsv_debug_vits_rows")
 
 
 def debug_sample(logits, seen, sampler: "Sampler", step: int):

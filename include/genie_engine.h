@@ -512,6 +512,93 @@ typedef struct gsv_rows_desc {
 } gsv_rows_desc;
 int gsv_debug_rows(const gsv_rows_desc* d, void* stream);
 
+/* One launch of the vocoder's conv entry (conv1d / conv1d_deferred, csrc/vits.hip) on device
+ * buffers, engine-free; the fields are those of ConvArgs (csrc/vits.h), which states the operation.
+ * Every pointer is a device pointer, 0 where the launch has none.
+ *   wh != 0: the f16-split path (k_conv_h / k_conv_ws), refused where it does not cover the shape;
+ *     wh == 0: the f32 kernel on w.
+ *   n_x, n_w, n_out, n_res, n_acc, n_out2, n_seg: the element counts of x, w (or wh), out, res, acc,
+ *     out2 (= res2) and seg as the caller allocated them; part_cap that of part.
+ *   dry != 0: check the arguments and report the form, launch nothing (no HIP call).
+ *   deferred != 0: conv1d_deferred; form[3] = the slab count it left in part (0: out is complete).
+ * form[0] = the path (1 f32 direct, 2 f32 split-K, 3 k_conv_h, 4 k_conv_ws); f32: form[1] = nsplit,
+ * form[2] = 1 with float4 weight loads; f16: form[1] = the channel chunk (32 / 8), form[2] = the tile
+ * candidate 0..3.
+ * GSV_E_ARG, before any HIP call: K outside the instantiated set, dil outside 1..5, a null pointer
+ * the mode dereferences, div == 0 for mode 8, seg with deferred, extents (n_t, o_tstride, o_toff,
+ * phases, o_len, strides) past the stated element counts, and on the f16 path a misaligned wh,
+ * Cin % 8 != 0 or x_ts != 1 (gsv_last_error names it). */
+typedef struct gsv_conv_desc {
+    int32_t Cin, Tin, Cout, K, dil, pad;
+    int32_t n_t, o_tstride, o_toff, o_len;
+    int32_t in_act, mode, split, phases;
+    int32_t tile_force, ws, dry, deferred;
+    float in_slope, div;
+    const float* x; int64_t x_cs, x_ts;
+    const float* w; const float* bias;
+    float* out; int64_t o_cs, o_ts;
+    const float* res; int64_t r_cs, r_ts;
+    const float* vec; float* acc; float* out2; const float* res2;
+    int64_t w_phase_stride;
+    float* part; int64_t part_cap;
+    const void* wh; const float* wscale; int32_t* ovf; int64_t wh_phase_stride; const float* in_scale;
+    const int32_t* seg; int64_t vec_sstride;
+    int64_t n_x, n_w, n_out, n_res, n_acc, n_out2, n_seg;
+} gsv_conv_desc;
+int gsv_debug_conv(const gsv_conv_desc* d, void* stream, int32_t form[4]);
+/* One fused ResBlock step (mrf_pair, csrc/vits_mrf.hip): the fields of MrfPairArgs and of its
+ * epilogue ConvArgs (res = r); n_r, n_out, n_acc the element counts of r, out and acc.  GSV_E_ARG
+ * with mrf_pair's reason where it does not cover the arguments, for a null buffer the mode uses,
+ * out aliasing r, misaligned weights and buffers smaller than C x T. */
+typedef struct gsv_mrf_desc {
+    int32_t T, C, K, dil, mode, Cout, n_t, o_len, o_tstride, o_toff;
+    float div; int32_t reserved;
+    const float* r;
+    const void* w1; const float* s1; const float* b1;
+    const void* w2; const float* s2; const float* bias2;
+    int32_t* ovf;
+    float* out; float* acc; const int32_t* seg;
+    int64_t o_cs, o_ts, r_cs, r_ts;
+    int64_t n_r, n_out, n_acc, n_seg;
+} gsv_mrf_desc;
+int gsv_debug_mrf_pair(const gsv_mrf_desc* d, void* stream);
+/* One launch of the vocoder's attention (mha, csrc/vits.hip): the fields of MhaArgs; row_seg_host
+ * = the host copy of row_seg ([nq][2], required with it); n_q, n_k, n_v, n_out the element counts.
+ * GSV_E_ARG: dk > 128, a row's key count outside 1..2048, window > 8, rel-pos terms with
+ * nq != nk and no row_seg (or a row outside its own key range), key ranges or strides that leave
+ * a buffer. */
+typedef struct gsv_mha_desc {
+    int32_t nq, nk, heads, dk, postdiv, window;
+    float scale; int32_t reserved;
+    const float* q; int64_t q_ts, q_cs;
+    const float* k; int64_t k_ts, k_cs;
+    const float* v; int64_t v_ts, v_cs;
+    float* out; int64_t o_ts, o_cs;
+    const float* ek; const float* ev;
+    const int32_t* row_seg; const int32_t* row_seg_host;
+    int64_t n_q, n_k, n_v, n_out;
+} gsv_mha_desc;
+int gsv_debug_mha(const gsv_mha_desc* d, void* stream);
+/* One launch of a row kernel of csrc/vits.hip on [C][T] device buffers.
+ *   op 0 ln_channels: out = LN_C(x + y) (y, seg optional) with g, b.
+ *   op 1 ln_channels_slabs: y = bias + the nsplit slabs [nsplit][C][T] in `y` (bias optional).
+ *   op 2 wn_gate: out [C][T] = tanh(x[c]) sigmoid(x[C + c]), x [2C][T].
+ *   op 3 wn_gate_slabs: the same of (bias + the nsplit slabs [nsplit][2C][T] in x) + vec (per seg).
+ *   op 4 mean3: out = ((x + y) + z) / div over n elements.
+ *   op 5 seg_fill: out (int32 [n]) from off, len (device int32 [nseg]) and the factor f.
+ * T == 0 (n == 0) returns 0 without a launch.  GSV_E_ARG for what the host entries abort on or
+ * cannot cover: C outside 1..256, seg or slabs with C % 16 != 0, nsplit < 2 (op 1) / < 1 (op 3),
+ * null pointers, nseg < 1, f < 1. */
+typedef struct gsv_vits_rows_desc {
+    int32_t op, C, T, nsplit, nseg, f;
+    int64_t n, vec_sstride;
+    float div; int32_t reserved;
+    const float* x; const float* y; const float* z; void* out;
+    const float* g; const float* b; const float* bias; const float* vec;
+    const int32_t* seg; const int32_t* off; const int32_t* len;
+} gsv_vits_rows_desc;
+int gsv_debug_vits_rows(const gsv_vits_rows_desc* d, void* stream);
+
 /* Probe: replay one kernel configuration `iters` times (hipGraph) between HIP
  * events on the engine stream; *us = average microseconds per launch.
  * which: 0/1 empty kernel (1/256 blocks), 2 QKV GEMV (+LN prologue), 3 QKV GEMV,
