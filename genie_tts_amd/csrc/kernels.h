@@ -143,6 +143,14 @@ struct AttnArgs {
     int ntiles;
 };
 void attn_rows(const AttnArgs& a, hipStream_t s);
+// The kernel attn_rows launches for `a` (the one statement of its rule; host only, no HIP call):
+// k_attn_flash for one sequence's rows, k_attn_rows as soon as rows name their sequence or may be
+// skipped, or with GENIE_ATTN_FLASH=0 (flash_enabled false; attn_flash_enabled() reads it once).
+enum AttnForm { ATTN_FORM_ROWS = 1, ATTN_FORM_FLASH = 2 };
+AttnForm attn_form(const AttnArgs& a, bool flash_enabled);
+bool attn_flash_enabled();
+// k_attn_flash whatever the rule says: 16 rows per block, or the tiles of a.tiles (<= 16 rows each)
+void attn_rows_flash(const AttnArgs& a, hipStream_t s);
 // Batched decode attention (one block per head x sequence) whose prologue reduces
 // the split-K QKV slabs of its head: q/k/v = b_in + sum_z slab[z][b][...] (fixed
 // order), appends the new K/V row at position kvlen[b], attends over [0, kvlen[b]].

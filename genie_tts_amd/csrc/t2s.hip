@@ -809,7 +809,10 @@ __global__ __launch_bounds__(256) void k_attn_rows(AttnArgs a, int len_add) {
 // softmax (#95), P.V (#96) as k_attn_rows.
 __global__ __launch_bounds__(256) void k_attn_dec_slabs(AttnDecArgs a) {
     __shared__ float p[ATTN_MAXT];
-    __shared__ float qs[32], kn[32], vn[32];
+    // kn is read as float4 beside the cache rows
+    __shared__ __attribute__((aligned(16))) float qs[32];
+    __shared__ __attribute__((aligned(16))) float kn[32];
+    __shared__ __attribute__((aligned(16))) float vn[32];
     __shared__ float red[16];
     __shared__ float part[8][33];
     const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
@@ -1345,17 +1348,34 @@ void attn_rows_rowlane(const AttnArgs& a, hipStream_t s) {
 
 // (One sequence's prefill stays on k_attn_flash: at ~300 rows a split-fp16 MFMA kernel's 80
 // blocks of 64 rows were no faster -- prefill 2.00 vs 1.91 ms, profiles/r04q_prefill_attn.txt.)
-void attn_rows(const AttnArgs& a, hipStream_t s) {
-    if (a.rows <= 0) return;
+AttnForm attn_form(const AttnArgs& a, bool flash_enabled) {
+    return flash_enabled && !a.row_seq && !a.row_skip ? ATTN_FORM_FLASH : ATTN_FORM_ROWS;
+}
+
+bool attn_flash_enabled() {
     static const bool flash = [] {
         const char* e = std::getenv("GENIE_ATTN_FLASH");
         return !(e && std::atoi(e) == 0);
     }();
-    if (flash && !a.row_seq && !a.row_skip) {
-        hipLaunchKernelGGL(k_attn_flash, dim3(16, (a.rows + AF_ROWS - 1) / AF_ROWS), dim3(256), 0, s, a);
-        return;
+    return flash;
+}
+
+void attn_rows(const AttnArgs& a, hipStream_t s) {
+    if (a.rows <= 0) return;
+    switch (attn_form(a, attn_flash_enabled())) {
+        case ATTN_FORM_FLASH:
+            hipLaunchKernelGGL(k_attn_flash, dim3(16, (a.rows + AF_ROWS - 1) / AF_ROWS), dim3(256), 0, s, a);
+            break;
+        case ATTN_FORM_ROWS:
+            hipLaunchKernelGGL(k_attn_rows, dim3(16, a.rows), dim3(256), 0, s, a, 0);
+            break;
     }
-    hipLaunchKernelGGL(k_attn_rows, dim3(16, a.rows), dim3(256), 0, s, a, 0);
+}
+
+void attn_rows_flash(const AttnArgs& a, hipStream_t s) {
+    const int nb = a.tiles ? a.ntiles : (a.rows + AF_ROWS - 1) / AF_ROWS;
+    if (nb <= 0) return;
+    hipLaunchKernelGGL(k_attn_flash, dim3(16, nb), dim3(256), 0, s, a);
 }
 
 void attn_rows_plus(const AttnArgs& a, int len_add, hipStream_t s) {

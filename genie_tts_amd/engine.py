@@ -224,6 +224,55 @@ class VitsRowsDesc(ctypes.Structure):
         (n, _VP) for n in ("x", "y", "z", "out", "g", "b", "bias", "vec", "seg", "off", "len")]
 
 
+class AttnDesc(ctypes.Structure):
+    """gsv_attn_desc: one launch of a T2S attention kernel."""
+    _fields_ = [(n, _I32) for n in ("form", "rows", "tmax", "len_add", "ntiles", "nslab", "dry", "reserved")] + [
+        ("scale", _F32), ("reserved2", _I32),
+        ("q", _VP), ("ldq", _I64), ("k", _VP), ("v", _VP), ("seq_stride", _I64),
+        ("row_len", _VP), ("row_len_host", _VP), ("row_seq", _VP), ("row_seq_host", _VP), ("row_skip", _VP),
+        ("out", _VP), ("ldo", _I64), ("tiles", _VP), ("tiles_host", _VP),
+        ("slabs", _VP), ("slab_stride", _I64), ("b_in", _VP)]
+
+
+class AttnOutDesc(ctypes.Structure):
+    """gsv_attn_out_desc: one attn_outproj launch."""
+    _fields_ = [("B", _I32), ("tmax", _I32), ("scale", _F32), ("reserved", _I32),
+                ("q", _VP), ("k", _VP), ("v", _VP), ("seq_stride", _I64),
+                ("kvlen", _VP), ("kvlen_host", _VP), ("done", _VP),
+                ("WoT", _VP), ("part", _VP), ("acc_out", _VP), ("acc_bstride", _I64)]
+
+
+class GemvDesc(ctypes.Structure):
+    """gsv_gemv_desc: one gemv_f16 launch."""
+    _fields_ = [(n, _I32) for n in ("B", "N", "K", "mode", "n_part", "kv_tmax", "kv_pos0", "reserved")] + [
+        ("src", _VP), ("lds", _I64),
+        ("part", _VP), ("part_stride", _I64), ("part_bias", _VP), ("part_res", _VP),
+        ("acc_in", _VP), ("acc_bstride", _I64),
+        ("ln_g", _VP), ("ln_b", _VP), ("ln_out", _VP), ("W", _VP), ("bias", _VP),
+        ("C", _VP), ("ldc", _I64), ("res", _VP), ("ldr", _I64),
+        ("kv_k", _VP), ("kv_v", _VP), ("kv_seq_stride", _I64),
+        ("kv_row_pos", _VP), ("kv_row_pos_host", _VP), ("kv_row_skip", _VP)]
+
+
+class FfnDesc(ctypes.Structure):
+    """gsv_ffn_desc: one ffn_fused launch."""
+    _fields_ = [("B", _I32), ("nslices", _I32)] + [
+        (n, _VP) for n in ("h", "bo", "attn_part", "acc_attn", "ln_g", "ln_b", "h1", "W1", "b1", "W2T", "part",
+                           "acc_out")] + [("acc_bstride", _I64)]
+
+
+class EmbedDesc(ctypes.Structure):
+    """gsv_embed_desc: one launch of an embedding kernel."""
+    _fields_ = [(n, _I32) for n in ("op", "n", "n_tok", "n_pe")] + [
+        ("tok", _VP), ("tok_host", _VP), ("ldy", _I64), ("ny", _VP), ("ny_host", _VP),
+        ("emb", _VP), ("alpha", _VP), ("pe", _VP), ("out", _VP), ("done", _VP), ("ssl", _VP)]
+
+
+# gsv_debug_attn's forms (the names it takes; "auto" reports "rows" or "flash") and gsv_debug_embed's ops
+ATTN_FORMS = ("auto", "rows", "flash", "rowlane", "mf32", "dec_slabs")
+EMBED_OPS = {"decode_embed": 0, "audio_embed_prompts": 1, "ssl_im2col": 2}
+ATTN_SCALE = math.sqrt(1.0 / math.sqrt(32.0))     # applied to q and to k (t2s_stage_decoder #91-94)
+
 # ConvMode (csrc/vits.h) and the paths gsv_debug_conv reports (ConvPath)
 CONV_MODES = {"store": 0, "relu": 1, "resid": 2, "vec": 3, "sub": 4, "tanh": 5, "acc_first": 6, "acc_add": 7,
               "acc_mean": 8, "resid_vec": 9, "split_resid": 10}
@@ -318,6 +367,11 @@ def lib():
         L.gsv_debug_mrf_pair.argtypes = [ctypes.POINTER(MrfDesc), vp]
         L.gsv_debug_mha.argtypes = [ctypes.POINTER(MhaDesc), vp]
         L.gsv_debug_vits_rows.argtypes = [ctypes.POINTER(VitsRowsDesc), vp]
+        L.gsv_debug_attn.argtypes = [ctypes.POINTER(AttnDesc), vp, ctypes.POINTER(ctypes.c_int32)]
+        L.gsv_debug_attn_out.argtypes = [ctypes.POINTER(AttnOutDesc), vp]
+        L.gsv_debug_gemv.argtypes = [ctypes.POINTER(GemvDesc), vp]
+        L.gsv_debug_ffn.argtypes = [ctypes.POINTER(FfnDesc), vp]
+        L.gsv_debug_embed.argtypes = [ctypes.POINTER(EmbedDesc), vp]
         _lib = L
     return _lib
 
@@ -337,6 +391,7 @@ EXPORTED = (
     "gsv_debug_interp_linear", "gsv_t2s_generate_each", "gsv_debug_sample_each",
     "gsv_audio_samples", "gsv_audio_convert", "gsv_debug_gemm", "gsv_debug_rows",
     "gsv_debug_conv", "gsv_debug_mrf_pair", "gsv_debug_mha", "gsv_debug_vits_rows",
+    "gsv_debug_attn", "gsv_debug_attn_out", "gsv_debug_gemv", "gsv_debug_ffn", "gsv_debug_embed",
 )
 
 
@@ -576,6 +631,71 @@ def debug_vits_rows(op: str, stream=True, **f):
     d.op, d.div = VITS_ROW_OPS[op] if isinstance(op, str) else op, 1.0
     _fill(d, f)
     _check(lib().gsv_debug_vits_rows(ctypes.byref(d), _stream() if stream else None), "gsv_debug_vits_rows")
+
+
+def _fill_host(d, f, names):
+    """_fill, with the host copies `names` (numpy arrays of the dtype given) kept alive by the list returned."""
+    keep = []
+    for k, dt in names.items():
+        h = f.pop(k, None)
+        if h is not None:
+            h = np.ascontiguousarray(h, dt)
+            keep.append(h)
+            setattr(d, k, h.ctypes.data)
+    _fill(d, f)
+    return keep
+
+
+def attn_desc(form="auto", dry=False, **f) -> AttnDesc:
+    """An AttnDesc from fields by name (form: a name of ATTN_FORMS); scale defaults to ATTN_SCALE,
+    ldq / ldo to 512.  row_len_host, row_seq_host, tiles_host: int32 arrays, referenced by d._keep."""
+    d = AttnDesc()
+    d.form, d.dry, d.scale, d.ldq, d.ldo = ATTN_FORMS.index(form) if isinstance(form, str) else form, int(dry), \
+        ATTN_SCALE, 512, 512
+    d._keep = _fill_host(d, f, {"row_len_host": np.int32, "row_seq_host": np.int32, "tiles_host": np.int32})
+    return d
+
+
+def debug_attn(form="auto", stream=True, **f) -> str:
+    """gsv_debug_attn: one launch of a T2S attention kernel on the current stream (stream = None
+    with dry=True: no HIP call); returns the form that ran (a name of ATTN_FORMS)."""
+    d = attn_desc(form, **f)
+    ran = ctypes.c_int32(-1)
+    _check(lib().gsv_debug_attn(ctypes.byref(d), _stream() if stream and not d.dry else None, ctypes.byref(ran)),
+           "gsv_debug_attn")
+    return ATTN_FORMS[ran.value]
+
+
+def debug_attn_out(**f):
+    """gsv_debug_attn_out: one attn_outproj launch; the fields of gsv_attn_out_desc by name."""
+    d = AttnOutDesc()
+    d.scale = ATTN_SCALE
+    keep = _fill_host(d, f, {"kvlen_host": np.int32})
+    _check(lib().gsv_debug_attn_out(ctypes.byref(d), _stream()), "gsv_debug_attn_out")
+    del keep
+
+
+def debug_gemv(mode="store", **f):
+    """gsv_debug_gemv: one gemv_f16 launch; the fields of gsv_gemv_desc by name (mode: a name of EPI)."""
+    d = GemvDesc()
+    d.mode = EPI[mode] if isinstance(mode, str) else mode
+    keep = _fill_host(d, f, {"kv_row_pos_host": np.int32})
+    _check(lib().gsv_debug_gemv(ctypes.byref(d), _stream()), "gsv_debug_gemv")
+    del keep
+
+
+def debug_ffn(**f):
+    """gsv_debug_ffn: one ffn_fused launch; the fields of gsv_ffn_desc by name."""
+    _check(lib().gsv_debug_ffn(ctypes.byref(_fill(FfnDesc(), f)), _stream()), "gsv_debug_ffn")
+
+
+def debug_embed(op: str, **f):
+    """gsv_debug_embed: one launch of an embedding kernel (a name of EMBED_OPS)."""
+    d = EmbedDesc()
+    d.op = EMBED_OPS[op] if isinstance(op, str) else op
+    keep = _fill_host(d, f, {"tok_host": np.int64, "ny_host": np.int32})
+    _check(lib().gsv_debug_embed(ctypes.byref(d), _stream()), "gsv_debug_embed")
+    del keep
 
 
 def debug_sample(logits, seen, sampler: "Sampler", step: int):

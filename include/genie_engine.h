@@ -599,6 +599,97 @@ typedef struct gsv_vits_rows_desc {
 } gsv_vits_rows_desc;
 int gsv_debug_vits_rows(const gsv_vits_rows_desc* d, void* stream);
 
+/* One launch of a T2S attention kernel (csrc/t2s.hip) on device buffers, engine-free.  16 heads of
+ * 32 dims; q [rows][ldq], K / V caches [16][tmax][32] per sequence, seq_stride elements apart;
+ * row r attends over keys [0, row_len[r] + len_add) of sequence row_seq[r] (0 without row_seq).
+ *   form 0 auto: attn_rows; *form = the kernel its rule (attn_form) picked, 1 or 2.
+ *   form 1 rows: k_attn_rows (attn_rows_plus with len_add, 0 allowed).  form 2 flash: k_attn_flash,
+ *     blocks of 16 rows or the tiles.  form 3 rowlane / 4 mf32: the packed-prefill kernels over
+ *     `tiles` ([ntiles][3] {sequence, first row, rows}).  form 5 dec_slabs: attn_decode_slabs;
+ *     rows = B, row_len = kvlen, row_skip = done, q = b_in + the sum of nslab slabs [B][1536]
+ *     slab_stride apart, the new K / V row appended at kvlen[b]; out [B][512].
+ *   row_len_host, row_seq_host, tiles_host: host copies of the device arrays (required with them):
+ *     the hook checks those.  len_add is form 1's alone and must be 0 elsewhere.
+ *   dry != 0: check and report the form, launch nothing (no HIP call).
+ * GSV_E_ARG before any HIP call: rows or tmax <= 0, a null buffer, a length outside [1, tmax] (or
+ * above 4096 for forms 1 and 5), q / k / v not 16-B aligned, ldq % 4, ldo % 4 or an unaligned out
+ * (forms 3, 4), seq_stride % 4 or below one cache with several sequences, forms 3 / 4 without
+ * tiles, a tile of more rows than a block holds (16 flash, 128 rowlane, 128 mf32), past `rows` or of
+ * a negative sequence, flash or auto-with-tiles misuse (gsv_last_error names it), and for form 5
+ * nslab < 1, null b_in / kvlen / done, kvlen[b] + 1 > tmax, overlapping slabs. */
+typedef struct gsv_attn_desc {
+    int32_t form, rows, tmax, len_add, ntiles, nslab, dry, reserved;
+    float scale; int32_t reserved2;
+    const float* q; int64_t ldq;
+    float* k; float* v; int64_t seq_stride;
+    const int32_t* row_len; const int32_t* row_len_host;
+    const int32_t* row_seq; const int32_t* row_seq_host;
+    const uint8_t* row_skip;
+    float* out; int64_t ldo;
+    const int32_t* tiles; const int32_t* tiles_host;
+    const float* slabs; int64_t slab_stride; const float* b_in;
+} gsv_attn_desc;
+int gsv_debug_attn(const gsv_attn_desc* d, void* stream, int32_t* form);
+/* One attn_outproj launch (csrc/t2s_decode.hip): sequence b attends over [0, kvlen[b] + 1) and the
+ * head's out-projection partial goes to part [16][B][512], or as fixed point (2^-32) into
+ * acc_out [b * acc_bstride + n].  GSV_E_ARG: B <= 0, null tensors, kvlen_host[b] + 1 outside
+ * [1, tmax], q / k / v / WoT not 16-B aligned, both or neither of part / acc_out, acc_bstride < 512
+ * with B > 1, seq_stride below one cache with B > 1. */
+typedef struct gsv_attn_out_desc {
+    int32_t B, tmax; float scale; int32_t reserved;
+    const float* q; const float* k; const float* v; int64_t seq_stride;
+    const int32_t* kvlen; const int32_t* kvlen_host; const uint8_t* done;
+    const void* WoT; float* part; int64_t* acc_out; int64_t acc_bstride;
+} gsv_attn_out_desc;
+int gsv_debug_attn_out(const gsv_attn_out_desc* d, void* stream);
+/* One gemv_f16 launch (csrc/t2s.hip): the fields of GemvArgs; kv_row_pos_host the host copy of
+ * kv_row_pos.  mode: 0 store, 1 relu, 2 resid, 3 qkv.  GSV_E_ARG: B outside [1, 8], K not 512 or
+ * 2048, N <= 0, a LayerNorm prologue (ln_g) with K != 512 or without ln_b, part / acc_in without
+ * ln_g (or both, or without part_bias / part_res), n_part no positive multiple of 16, a plain
+ * prologue with lds % 4 or an unaligned or null src, W not 16-B aligned, null C, resid without res,
+ * qkv with N != 1536, without caches or with a position outside [0, kv_tmax), another mode. */
+typedef struct gsv_gemv_desc {
+    int32_t B, N, K, mode, n_part, kv_tmax, kv_pos0, reserved;
+    const float* src; int64_t lds;
+    const float* part; int64_t part_stride; const float* part_bias; const float* part_res;
+    const int64_t* acc_in; int64_t acc_bstride;
+    const float* ln_g; const float* ln_b; float* ln_out;
+    const void* W; const float* bias;
+    float* C; int64_t ldc;
+    const float* res; int64_t ldr;
+    float* kv_k; float* kv_v; int64_t kv_seq_stride;
+    const int32_t* kv_row_pos; const int32_t* kv_row_pos_host; const uint8_t* kv_row_skip;
+} gsv_gemv_desc;
+int gsv_debug_gemv(const gsv_gemv_desc* d, void* stream);
+/* One ffn_fused launch (csrc/t2s_decode.hip): the fields of FfnArgs; the attention hand-off comes
+ * as floats (attn_part [16][B][512]) or fixed point (acc_attn), the result leaves as floats
+ * (part [nslices][B][512]) or fixed point (acc_out).  GSV_E_ARG: nslices not 32 or 64, B outside
+ * [1, 8], null tensors, both or neither of each hand-off pair, W1 / W2T not 16-B aligned,
+ * acc_bstride < 512 with B > 1 and a fixed-point hand-off. */
+typedef struct gsv_ffn_desc {
+    int32_t B, nslices;
+    const float* h; const float* bo; const float* attn_part; const int64_t* acc_attn;
+    const float* ln_g; const float* ln_b; float* h1;
+    const void* W1; const float* b1; const void* W2T;
+    float* part; int64_t* acc_out; int64_t acc_bstride;
+} gsv_ffn_desc;
+int gsv_debug_ffn(const gsv_ffn_desc* d, void* stream);
+/* One launch of an exact f32 embedding kernel of csrc/t2s.hip.
+ *   op 0 decode_embed: out[b] = emb[tok[b][ny[b] - 1]] + alpha pe[ny[b]] for n = B sequences
+ *     (tok [B][ldy] int64, done optional); tok_host / ny_host the host copies.
+ *   op 1 audio_embed_prompts: out[p] = emb[tok[p]] + alpha pe[p + 1], p < n.
+ *   op 2 ssl_im2col: out[t][2 ci + j] = ssl[ci][2 t + j], ci < 768, t < n / 2 (n = n_ssl).
+ * emb is fp16 [n_tok][512], pe [n_pe][512].  GSV_E_ARG: n <= 0, null tensors, a token outside
+ * [0, n_tok), ny[b] outside [1, ldy] or a pe row at or past n_pe. */
+typedef struct gsv_embed_desc {
+    int32_t op, n, n_tok, n_pe;
+    const int64_t* tok; const int64_t* tok_host; int64_t ldy;
+    const int32_t* ny; const int32_t* ny_host;
+    const void* emb; const float* alpha; const float* pe;
+    float* out; const uint8_t* done; const float* ssl;
+} gsv_embed_desc;
+int gsv_debug_embed(const gsv_embed_desc* d, void* stream);
+
 /* Probe: replay one kernel configuration `iters` times (hipGraph) between HIP
  * events on the engine stream; *us = average microseconds per launch.
  * which: 0/1 empty kernel (1/256 blocks), 2 QKV GEMV (+LN prologue), 3 QKV GEMV,
