@@ -39,9 +39,13 @@
 // {tag, v0, v1, v2} -- three consecutive columns and their tag in one write-through
 // store, swept by 16-byte loads (MI355X_MICROARCH.md: 8-byte accesses run at
 // 0.54-0.70x the 16-byte rate; tools/xcd_handoff.hip on this pattern: a 16-producer
-// row sweep 1.55 us vs 1.98 us with 8-byte {tag, value} granules).  Two threads poll
-// each column group (half of the rows each; the second continues the first's sum in
-// row order), so the poll registers stay small.  The logits candidates and the token
+// row sweep 1.55 us vs 1.98 us with 8-byte {tag, value} granules).  Two lanes of ONE
+// wave poll each column group (lane i rows 0..7, lane 32 + i rows 8..16 at the same
+// time), so the poll registers stay small (9 granules per lane); the high lane takes the
+// low lane's sums by a 32-lane swap and continues them in row order (gather_halves), so
+// a hop has one block barrier behind its poll, the one that publishes the operand row
+// to the MFMA waves -- no LDS round trip and no barrier between the halves.  Waves 0, 1,
+// 2, 4, 5, 6 poll (32 column groups each); 3 and 7 do not.  The logits candidates and the token
 // keep 8-byte granules (persist.h).  tag = (epoch << 12) | (step + 1) in a ring of
 // RING1 step slots.  Every sum is formed in a fixed order, so results do not depend
 // on arrival order.  Every spin is bounded; a timeout sets the error word and every
@@ -130,11 +134,15 @@ __device__ __forceinline__ u32x4 ld_g16(const W& ws, int off) {   // buffer_load
 
 // One lane waits for N 16-byte granules off + k * stride (k < N), all N loads in
 // flight; re-polls only the stale ones (persist.h wait_gran_n with 16-byte granules).
+// A lane with `last` false leaves granule N - 1 out (the lanes of one wave that poll
+// N - 1 and N rows, gather_halves).
 template <int N, class W>
 __device__ __forceinline__ void wait_g16_n(const W& ws, int off, int stride, unsigned tag, u32x4 (&g)[N], int* err,
-                                           bool& ok, unsigned long long ticks) {
+                                           bool& ok, unsigned long long ticks, bool last = true) {
 #pragma unroll
-    for (int k = 0; k < N; ++k) g[k] = ld_g16(ws, off + k * stride);
+    for (int k = 0; k < N - 1; ++k) g[k] = ld_g16(ws, off + k * stride);
+    if (last) g[N - 1] = ld_g16(ws, off + (N - 1) * stride);
+    else g[N - 1] = u32x4{tag, 0u, 0u, 0u};
     unsigned long long t0 = 0;
     for (unsigned it = 0;; ++it) {
         bool all = true;
@@ -182,7 +190,8 @@ __device__ __forceinline__ void wait_tag16_slow(const u64* p, unsigned tag, int*
 // registers live across the layer loop -- the kernel sits at the 256-VGPR limit).
 struct Shared1 {
     float pk[PWV][64];              // per-wave staging of 64 published columns (16-byte granules)
-    float hs[3 * GQ];               // partial row sums of the first poll half (hop B / hop A)
+    float hs[3 * GQ];               // unused (the poll halves' partial sums went through here); kept: the
+                                    // offsets below are relied on (t2s_persistm.hip, the *_each units)
     float h1s[32];                  // h1 block j of an FFN workgroup, staged for its 11 granules
     float qkv[96];
     _Float16 osh[PWV][32], osl[PWV][32];   // MFMA row operand: head output split hi + lo (out-projection),
@@ -397,6 +406,12 @@ __device__ __forceinline__ float swap_sum16(float x) {
 __device__ __forceinline__ float swap_sum32(float x) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+// lane 32 + i: lane i's x (v_permlane32_swap of a register with itself: result 0 keeps the
+// low lanes and holds their values again in the high lanes)
+__device__ __forceinline__ float from_low32(float x) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    return __uint_as_float(r[0]);
 }
 
 // Head output from the 8 wave partials (m_w, l_w in sh.wred, o_w in sh.at.ov4),
@@ -653,9 +668,12 @@ __device__ __forceinline__ void pf_wait(int ticks) {
 // LN2 of layer l - 1 -> sh.p2 (call from every wave; l > 0).  The single-sequence kernel:
 // waves 0..5 (its fenced barriers order the DMAs long before the next owned layer reads
 // them).  The multi-sequence kernel (POLLERS): waves 0, 1, 2, 4, 5, 6, the hop-B gather's
-// polling waves, whose in-order vmcnt waits retire these DMAs before the gather's last
-// barrier, after which sh.p2 is read -- waves 3 and 7 never poll and that kernel has no
-// fenced barrier between a prefetch and the next gather.  (Hardening found while looking
+// polling waves, whose in-order vmcnt waits retire these DMAs before the gather's
+// barrier, after which sh.p2[2] is read -- waves 3 and 7 never poll and that kernel has no
+// fenced barrier between a prefetch and the next gather.  sh.p2[0] / [1] are read by the
+// gather's column owners BEFORE that barrier, for columns another wave fetched: there
+// gather_pfh<NF> itself waits for vmcnt(0) and holds a barrier before a layer's first
+// poll.  (Hardening found while looking
 // for the r05 persist1m deviation, profiles/r05x_persist1m_deviation.txt; it did not
 // change that case.  The single-sequence kernel keeps its assignment: moving its DMAs
 // cost ~0.25 ms per launch, r05b.)
@@ -672,50 +690,80 @@ __device__ __forceinline__ void dma_ln2(const PLayer& Q, Shared1& sh, int w, int
     }
 }
 
+// One hand-off column group per lane pair of ONE wave: sums rows 0..15 of granule column q
+// of the 16-byte rows at byte offset row0 (row stride Ws1::ROW * 8) in row order.  The
+// polling waves are 0, 1, 2, 4, 5, 6 (3 and 7 never poll: is_pub_wave, dma_ln2<POLLERS>);
+// the k-th of them owns columns 32 k .. 32 k + 31 (k = 5: 160 .. 175).  Lane i < 32 polls
+// rows 0..7 of column 32 k + i and forms f = row 0, += rows 1..7; lane 32 + i polls rows
+// 8..15 (N = 9: and row 16 -> x) at the same time, takes f from lane i by a 32-lane swap --
+// no LDS round trip and no block barrier between the halves -- and continues += rows 8..15:
+// bit-identical to one thread summing rows 0..15.  Returns true in the lanes 32 + i that own
+// a column group, which hold f[0..2] (and x); every lane of the block must call it.
+template <int N, class W>
+__device__ __forceinline__ bool gather_halves(const PersistArgs& a, const W& ws, int tid, int row0, unsigned tag,
+                                              bool& ok, int& q, float (&f)[3], u32x4& x) {
+    constexpr int RB = (int)Ws1::ROW * 8;   // bytes per row
+    const int w = tid >> 6, lane = tid & 63;
+    const bool hi = lane >= 32;
+    q = 32 * (w - (w >> 2)) + (lane & 31);
+    const bool act = (w & 3) != 3 && q < GQ;
+    u32x4 g[N];
+    float p0 = 0.f, p1 = 0.f, p2 = 0.f;
+    if (act) {
+        wait_g16_n<N>(ws, row0 + 16 * q + (hi ? 8 * RB : 0), RB, tag, g, a.err, ok, a.spin_ticks, N == 8 || hi);
+        p0 = __uint_as_float(g[0].y), p1 = __uint_as_float(g[0].z), p2 = __uint_as_float(g[0].w);
+#pragma unroll
+        for (int r = 1; r < 8; ++r) {
+            p0 += __uint_as_float(g[r].y);
+            p1 += __uint_as_float(g[r].z);
+            p2 += __uint_as_float(g[r].w);
+        }
+    }
+    // the whole wave (no lane masked off): lanes 32 + i receive lane i's sums
+    const float lo[3] = {from_low32(p0), from_low32(p1), from_low32(p2)};
+    if (!(act && hi)) return false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        f[k] = lo[k];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) f[k] += __uint_as_float(g[r][1 + k]);
+    }
+    x = g[N - 1];
+    return true;
+}
+
 // Hop B: u = h1_{l-1} + (b2 + sum_j PF[l-1][j]) (l >= 1; the partials summed in
 // slice order) -> sh.lnb[0], and with `split` the MFMA operand split of u * n2w ->
 // sh.xh / sh.xl; lp2 = LDS rows {b2, scale, shift} of LN2_{l-1}.  A sleeping lane
-// waits for the wake-up granule (layer l-2's output); then thread q < GQ polls rows
-// 0..7 of granule column q and thread 256 + q rows 8..16, continuing the first
-// thread's sums in row order (bit-identical to one thread summing rows 0..15).
-// Ends with a block barrier.
+// waits for the wake-up granule (layer l-2's output); then the polling waves sum the
+// column groups (gather_halves, the h1 row as row 16).  Ends with a block barrier, the
+// only one behind the poll.  The column owners read lp2 BEFORE that barrier: the
+// single-sequence kernel's fenced barriers (step_start, the wake-up) lie between the
+// LN2 LDS-DMAs (dma_ln2) and this read; the multi-sequence kernel (NF), which has no
+// fenced barrier there, retires every wave's DMAs and holds a barrier before the first
+// sequence of a layer polls.
 template <class W, bool NF = false>
 __device__ __forceinline__ bool gather_pfh(const PersistArgs& a, const W& ws, int s, int l, const float* lp2,
                                            Shared1& sh, bool split, bool wake = true) {
-    const int tid = threadIdx.x, q = tid & 255;
+    const int tid = threadIdx.x;
     const unsigned tag = ws.tag(s);
-    constexpr int RB = (int)Ws1::ROW * 8;   // bytes per row
     bool ok = true;
+    if (NF && wake) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's LN2 (and K/V) LDS-DMAs landed
     if (l >= 2 && wake) {   // (a sequence that follows another through this layer polls at once)
         if (tid == 0) wait_tag16_slow(ws.at(ws.PFH(s, l - 2, 0)), tag, a.err, ok, a.spin_ticks);
         if (!block_ok_t<NF>(ok, sh)) return false;
+    } else if (NF && wake) {
+        bar_nf();
     }
-    const int off = ws.PFH(s, l - 1, 0) + 16 * q;
-    u32x4 g[9];
-    if (tid < GQ) {
-        u32x4 h[8];
-        wait_g16_n<8>(ws, off, RB, tag, h, a.err, ok, a.spin_ticks);
-        float f0 = __uint_as_float(h[0].y), f1 = __uint_as_float(h[0].z), f2 = __uint_as_float(h[0].w);
-#pragma unroll
-        for (int r = 1; r < 8; ++r) {
-            f0 += __uint_as_float(h[r].y);
-            f1 += __uint_as_float(h[r].z);
-            f2 += __uint_as_float(h[r].w);
-        }
-        sh.hs[3 * q] = f0; sh.hs[3 * q + 1] = f1; sh.hs[3 * q + 2] = f2;
-    } else if (tid >= 256 && q < GQ) {
-        wait_g16_n<9>(ws, off + 8 * RB, RB, tag, g, a.err, ok, a.spin_ticks);
-    }
-    if (!block_ok_t<NF>(ok, sh)) return false;
-    if (tid >= 256 && q < GQ) {
+    int q;
+    float f[3];
+    u32x4 g8;
+    if (gather_halves<9>(a, ws, tid, ws.PFH(s, l - 1, 0), tag, ok, q, f, g8)) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             if (k == 2 && gq_n(q) == 2) break;
-            float f = sh.hs[3 * q + k];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) f += __uint_as_float(g[r][1 + k]);
             const int c = gq_col(q, k);
-            const float u = __uint_as_float(g[8][1 + k]) + (lp2[c] + f);
+            const float u = __uint_as_float(g8[1 + k]) + (lp2[c] + f[k]);
             sh.lnb[0][c] = u;
             if (split) {
                 const float un = u * lp2[512 + c];
@@ -1095,39 +1143,25 @@ __device__ void run_ffn(const PersistArgs& a, const Ws1& ws, Shared1& sh, int gr
             // MFMA operand split of v * n1w: FFN1 runs on it while the LN1 statistics are
             // formed (W1 h1 + b1 = rden (W1 (v n1w) - mean W1 n1w) + (W1 n1b + b1), the
             // constant vectors folded at load time, as form_u)
-            // (hop A: thread q < GQ sums heads 0..7 of granule column q, thread 256 + q
-            // continues with heads 8..15 and forms the column group's v / operand split)
+            // (hop A: gather_halves over the 16 heads' rows; the column owners form the column
+            // group's v / operand split.  They read other threads' xr / bo / n1w, so those are
+            // behind a barrier of their own, held before the poll while the head partials
+            // are still on their way)
             {
                 bool ok = true;
-                constexpr int RB = (int)Ws1::ROW * 8;
-                const int q = tid & 255, off = ws.PA(s, l, 0) + 16 * q;
                 sh.ff.xr[tid] = xv;
                 sh.ff.bo[tid] = bo;
                 sh.ff.n1w[tid] = n1w;
-                u32x4 g[8];
-                if (tid < GQ) {
-                    wait_g16_n<8>(ws, off, RB, tag, g, a.err, ok, a.spin_ticks);
-                    float f0 = __uint_as_float(g[0].y), f1 = __uint_as_float(g[0].z), f2 = __uint_as_float(g[0].w);
-#pragma unroll
-                    for (int r = 1; r < 8; ++r) {
-                        f0 += __uint_as_float(g[r].y);
-                        f1 += __uint_as_float(g[r].z);
-                        f2 += __uint_as_float(g[r].w);
-                    }
-                    sh.hs[3 * q] = f0; sh.hs[3 * q + 1] = f1; sh.hs[3 * q + 2] = f2;
-                } else if (tid >= 256 && q < GQ) {
-                    wait_g16_n<8>(ws, off + 8 * RB, RB, tag, g, a.err, ok, a.spin_ticks);
-                }
-                if (!block_ok1(ok, sh)) return;
-                if (tid >= 256 && q < GQ) {
+                __syncthreads();
+                int q;
+                float sum[3];
+                u32x4 g7;
+                if (gather_halves<8>(a, ws, tid, ws.PA(s, l, 0), tag, ok, q, sum, g7)) {
 #pragma unroll
                     for (int k = 0; k < 3; ++k) {
                         if (k == 2 && gq_n(q) == 2) break;
-                        float sum = sh.hs[3 * q + k];
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) sum += __uint_as_float(g[r][1 + k]);
                         const int c = gq_col(q, k);
-                        const float vc = sh.ff.xr[c] + (sh.ff.bo[c] + sum);
+                        const float vc = sh.ff.xr[c] + (sh.ff.bo[c] + sum[k]);
                         sh.lnb[1][c] = vc;
                         const float un = vc * sh.ff.n1w[c];
                         if (!split_h(un, sh.xh[c], sh.xl[c]) || !(fabsf(un) < a.f16_limit)) {
@@ -1819,42 +1853,27 @@ __device__ void run_ffn_m(const PersistArgs& a, const WsSeq& base, Shared1& sh, 
                     bool ok = true;
                     // the first live sequence: a sleeping lane waits for the layer's attention
                     // input (the head partials follow about one pass later), then all poll
+                    // (the layer's bo / n1w, which the hop's column owners read for other threads'
+                    // columns, go to LDS behind this barrier: once per layer)
                     if (b == next_live(live, 0)) {
+                        sh.ff.bo[tid] = bo;
+                        sh.ff.n1w[tid] = n1w;
                         if (tid == 0) wait_tag16_slow(ws.at(l > 0 ? ws.PFH(s, l - 1, 0) : ws.PA(s, 0, 0)), tag, a.err,
                                                       ok, a.spin_ticks);
                         if (!block_ok_t<true>(ok, sh)) return;
                     }
                     MSTAMP(0);
-                    constexpr int RB = (int)Ws1::ROW * 8;
-                    const int q = tid & 255, off = ws.PA(s, l, 0) + 16 * q;
-                    sh.ff.bo[tid] = bo;
-                    sh.ff.n1w[tid] = n1w;
-                    u32x4 g[9];   // (second half: rows 8..15 and x_l)
-                    if (tid < GQ) {
-                        u32x4 h8[8];
-                        wait_g16_n<8>(ws, off, RB, tag, h8, a.err, ok, a.spin_ticks);
-                        float f0 = __uint_as_float(h8[0].y), f1 = __uint_as_float(h8[0].z), f2 = __uint_as_float(h8[0].w);
-#pragma unroll
-                        for (int r = 1; r < 8; ++r) {
-                            f0 += __uint_as_float(h8[r].y);
-                            f1 += __uint_as_float(h8[r].z);
-                            f2 += __uint_as_float(h8[r].w);
-                        }
-                        sh.hs[3 * q] = f0; sh.hs[3 * q + 1] = f1; sh.hs[3 * q + 2] = f2;
-                    } else if (tid >= 256 && q < GQ) {
-                        wait_g16_n<9>(ws, off + 8 * RB, RB, tag, g, a.err, ok, a.spin_ticks);
-                    }
-                    if (!block_ok_t<true>(ok, sh)) return;
+                    int q;
+                    float sum[3];
+                    u32x4 g8;   // (row 16: x_l)
+                    const bool own = gather_halves<9>(a, ws, tid, ws.PA(s, l, 0), tag, ok, q, sum, g8);
                     MSTAMP(1);
-                    if (tid >= 256 && q < GQ) {
+                    if (own) {
 #pragma unroll
                         for (int k = 0; k < 3; ++k) {
                             if (k == 2 && gq_n(q) == 2) break;
-                            float sum = sh.hs[3 * q + k];
-#pragma unroll
-                            for (int r = 0; r < 8; ++r) sum += __uint_as_float(g[r][1 + k]);
                             const int c = gq_col(q, k);
-                            const float vc = __uint_as_float(g[8][1 + k]) + (sh.ff.bo[c] + sum);
+                            const float vc = __uint_as_float(g8[1 + k]) + (sh.ff.bo[c] + sum[k]);
                             sh.lnb[1][c] = vc;
                             const float un = vc * sh.ff.n1w[c];
                             if (!split_h(un, sh.xh[c], sh.xl[c]) || !(fabsf(un) < a.f16_limit)) {
