@@ -250,6 +250,13 @@ def _out_rate(sample_rate, pcm16: bool = False) -> dict:
     return check_out_format(sample_rate, pcm16)
 
 
+def _loudness(loudness, peak) -> dict:
+    """The loudness keywords of a synthesis call: nothing when loudness is None (today's call,
+    unchanged), ValueError for a target outside -50 .. -5 LUFS or a ceiling outside (0, 1]."""
+    from .engine import check_loudness
+    return check_loudness(loudness, peak)
+
+
 def _sampling(top_k=None, top_p=None, temperature=None, repetition_penalty=None, seed=None) -> dict:
     """The sampling keywords of a synthesis call that were given, validated (ValueError for
     a value the engine rejects) before anything is synthesized."""
@@ -339,12 +346,18 @@ def tts(character_name: str, text: Union[str, Sequence[int], np.ndarray], play: 
         text_bert: Optional[np.ndarray] = None, sampler=None, speed: float = 1.0, *,
         top_k: Optional[int] = None, top_p: Optional[float] = None, temperature: Optional[float] = None,
         repetition_penalty: Optional[float] = None, seed: Optional[int] = None,
-        sample_rate: Optional[int] = None) -> Optional[np.ndarray]:
+        sample_rate: Optional[int] = None, loudness: Optional[float] = None,
+        peak: Optional[float] = None) -> Optional[np.ndarray]:
     """Internal.py:265-310 (TTSPlayer session: split, synthesize each sentence, save the
     concatenation as 16-bit WAV).  Returns the audio f32 [sum 1280*G_i] at 32 kHz.
     sample_rate: 8000, 16000, 22050, 24000, 32000, 44100 or 48000 (ValueError otherwise): the audio
     is returned, saved (the WAV header carries the rate) and played at that rate, each sentence
     resampled on the GPU behind its vocoder (Engine.audio_convert); None: 32 kHz, today's path.
+    loudness: a target in LUFS (-50 .. -5; ITU-R BS.1770-4 gated loudness, e.g. -16 for speech or
+    EBU R 128's -23): every sentence is measured on the GPU behind its vocoder and scaled to it,
+    in front of the rate conversion, the gain limited so that the sample peak stays under `peak`
+    (linear, (0, 1]; None: -1 dBFS).  With loudness alone the audio is float32 at 32 kHz,
+    normalised; None: the level the voice happens to have, today's path.  ValueError for a bad value.
     speed: the speech rate (GPT-SoVITS's `speed`, 0.25 .. 4; ValueError otherwise): sentence i
     is 640 * Engine.vits_frames(G_i, speed) samples, its pitch unchanged.
     top_k (1..64), top_p (0 < p <= 1, nucleus sampling), temperature (> 0), repetition_penalty
@@ -352,6 +365,7 @@ def tts(character_name: str, text: Union[str, Sequence[int], np.ndarray], play: 
     one, of the character's sampler), a value overrides it on a copy.  ValueError for a bad value."""
     rate = _rate(speed)
     rate.update(_out_rate(sample_rate))
+    rate.update(_loudness(loudness, peak))
     out_rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
     fields = _sampling(top_k, top_p, temperature, repetition_penalty, seed)
     if character_name not in _reference_audios:
@@ -376,14 +390,17 @@ async def tts_async(character_name: str, text: str, play: bool = False, split_se
                     save_path: Union[str, os.PathLike, None] = None, speed: float = 1.0, *, sampler=None,
                     top_k: Optional[int] = None, top_p: Optional[float] = None,
                     temperature: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                    seed: Optional[int] = None, sample_rate: Optional[int] = None) -> AsyncIterator[bytes]:
+                    seed: Optional[int] = None, sample_rate: Optional[int] = None,
+                    loudness: Optional[float] = None, peak: Optional[float] = None) -> AsyncIterator[bytes]:
     """Internal.py:193-262: yields one raw 16-bit PCM chunk per sentence as soon as it
     is synthesized (TTSPlayer chunk callback), the engine running off the event loop.
     speed, sampler and the sampling keywords: as for tts.  sample_rate (as for tts): the chunks
     are the int16 samples at that rate as the GPU's output stage wrote them (32000 gives the
-    bytes of the call without it); None: today's path, converted on the host."""
+    bytes of the call without it); None: today's path, converted on the host.  loudness / peak (as
+    for tts): each chunk normalised on the GPU in front of that conversion."""
     rate = _rate(speed)
     rate.update(_out_rate(sample_rate, pcm16=True))
+    rate.update(_loudness(loudness, peak))
     out_rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
     fields = _sampling(top_k, top_p, temperature, repetition_penalty, seed)
     if character_name not in _reference_audios:

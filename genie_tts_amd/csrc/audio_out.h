@@ -27,6 +27,7 @@ struct AudioOutItem {
     int n_in, n_out;
     int rate;           // index into AudioRates
     int format;         // 0 float32, 1 int16
+    const float* gain;  // device scalar of the loudness stage: y * gain before the conversion; null: none
 };
 
 int audio_rate_index(int out_rate);              // 0 -> 32000; -1: unsupported

@@ -62,6 +62,7 @@ __global__ __launch_bounds__(AO_TILE) void k_audio_out(AudioRates R, const Audio
         }
     }
     if (k >= it.n_out) return;
+    if (it.gain) y = y * *it.gain;   // loudness normalisation: one rounded multiply behind the chain
     if (it.format == 0) {
         ((float*)it.dst)[k] = y;
     } else {   // (x * 32767).astype(int16) of the reference, saturated
@@ -138,6 +139,7 @@ int gsv_engine::audio_out_init() {
             return set_error(GSV_E_HIP, "output stage tables");
         ao_rates.tab[i] = d;
     }
+    if (int r = loudness_init()) return r;
     ao_tab = (AudioOutItem*)dalloc(sizeof(AudioOutItem) * AO_SLOTS);
     if (!ao_tab || hipHostMalloc((void**)&ao_pin, sizeof(AudioOutItem) * AO_SLOTS, hipHostMallocDefault) != hipSuccess)
         return set_error(GSV_E_HIP, "output stage item table");
@@ -151,7 +153,7 @@ int gsv_engine::audio_item(const gsv_vits_item& u, AudioOutItem* a) const {
     const int rate = audio_rate_index(u.out_rate), T = vits_frames(u.n_sem, u.speed);
     if (rate < 0 || u.out_format < 0 || u.out_format > 1 || T < 0) return GSV_E_ARG;
     const int n_in = 640 * T;
-    *a = AudioOutItem{u.audio, u.out, n_in, (int)audio_samples(n_in, u.out_rate), rate, u.out_format};
+    *a = AudioOutItem{u.audio, u.out, n_in, (int)audio_samples(n_in, u.out_rate), rate, u.out_format, nullptr};
     return 0;
 }
 
@@ -159,8 +161,10 @@ int gsv_engine::audio_item(const gsv_vits_item& u, AudioOutItem* a) const {
 // the item table this call site owns (AO_SYNC: the engine stream's synchronous calls, AO_ASYNC:
 // the overlapped vocoder call, AO_BATCH_AT: a batch): a region is refilled only after the launch
 // that last read it has finished, which it has in practice (the wait is for the previous call's
-// stage, and a vocoder pass lies between two of them).
-int gsv_engine::audio_out(const AudioOutItem* items, int n, int region, hipStream_t s) {
+// stage, and a vocoder pass lies between two of them).  norm (null: none) lies beside items: the
+// entries with a target are measured first, one pass per launch (loudness.hip), and their
+// conversions read the gain from the measurement's slot on the device.
+int gsv_engine::audio_out(const AudioOutItem* items, const gsv_loudness* norm, int n, int region, hipStream_t s) {
     if (!ao_tab) return set_error(GSV_E_STATE, "output stage not initialised");
     const int base = region, cap = region == AO_BATCH_AT ? AO_BATCH : 1;   // (a region is its first slot)
     hipEvent_t ev = ao_ev[region];
@@ -169,10 +173,20 @@ int gsv_engine::audio_out(const AudioOutItem* items, int n, int region, hipStrea
         const int m = std::min(cap, n - i);
         if (hipEventSynchronize(ev) != hipSuccess) return set_error(GSV_E_HIP, "output stage wait");
         int max_out = 0;
+        std::vector<LoudItem> loud;
         for (int j = 0; j < m; ++j) {
             ao_pin[base + j] = items[i + j];
             max_out = std::max(max_out, items[i + j].n_out);
+            if (!norm || norm[i + j].target == 0.f) continue;
+            // measured into slot base + j, whose gain this item's conversion reads on the device
+            const gsv_loudness& l = norm[i + j];
+            loud.resize(m, LoudItem{nullptr, nullptr, -1, 0.f, 1.f, 0});
+            loud[j] = LoudItem{items[i + j].src, l.stats, items[i + j].n_in, l.target,
+                               l.peak == 0.f ? 0.8912509381337456f : l.peak, 0};
+            ao_pin[base + j].gain = lo_ws.stats + (size_t)(base + j) * LD_STATS + 2;
         }
+        if (!loud.empty())
+            if (int r = loudness_measure(loud.data(), m, base, s)) return r;
         hipMemcpyAsync(ao_tab + base, ao_pin + base, sizeof(AudioOutItem) * m, hipMemcpyHostToDevice, s);
         audio_out_launch(ao_rates, ao_tab + base, m, max_out, s);
         hipEventRecord(ev, s);
@@ -181,14 +195,16 @@ int gsv_engine::audio_out(const AudioOutItem* items, int n, int region, hipStrea
 }
 
 // The items of a vocoder call that carry `out`, converted from their final `audio`.
-int gsv_engine::audio_out_items(const gsv_vits_item* it, int n, int region, hipStream_t s) {
+int gsv_engine::audio_out_items(const gsv_vits_item* it, const gsv_loudness* norm, int n, int region, hipStream_t s) {
     std::vector<AudioOutItem> a;
+    std::vector<gsv_loudness> l;
     for (int i = 0; i < n; ++i) {
         if (!it[i].out) continue;
         a.emplace_back();
         if (audio_item(it[i], &a.back())) return set_error(GSV_E_ARG, "bad output rate or format");
+        if (norm) l.push_back(norm[i]);
     }
-    return a.empty() ? 0 : audio_out(a.data(), (int)a.size(), region, s);
+    return a.empty() ? 0 : audio_out(a.data(), norm ? l.data() : nullptr, (int)a.size(), region, s);
 }
 
 extern "C" int gsv_audio_samples(int32_t n_in, int32_t out_rate) {
@@ -205,6 +221,23 @@ extern "C" int gsv_audio_convert(gsv_engine* eng, const float* audio_32k, int32_
     if (n_in > 0 && (!audio_32k || !out)) return set_error(GSV_E_ARG, "null audio buffer");
     hipSetDevice(eng->device);
     StreamScope sc(eng, stream);
-    const AudioOutItem a{audio_32k, out, n_in, n_out, rate, out_format};
-    return eng->audio_out(&a, 1, gsv_engine::AO_SYNC, sc.st());
+    const AudioOutItem a{audio_32k, out, n_in, n_out, rate, out_format, nullptr};
+    return eng->audio_out(&a, nullptr, 1, gsv_engine::AO_SYNC, sc.st());
+}
+
+extern "C" int gsv_audio_normalize(gsv_engine* eng, const float* audio_32k, int32_t n_in, float target, float peak,
+                                   int32_t out_rate, int32_t out_format, void* out, float* stats, void* stream) {
+    if (!eng) return set_error(GSV_E_ARG, "null engine");
+    const int rate = audio_rate_index(out_rate), n_out = gsv_audio_samples(n_in, out_rate);
+    if (rate < 0 || n_out < 0) return set_error(GSV_E_ARG, "out_rate: 8000, 16000, 22050, 24000, 32000, 44100 or 48000");
+    if (out_format < 0 || out_format > 1) return set_error(GSV_E_ARG, "out_format: 0 (float32) or 1 (int16)");
+    const gsv_loudness l{target, peak, stats};
+    if (target == 0.f) return set_error(GSV_E_ARG, "loudness target: -50 .. -5 LUFS");
+    if (int r = check_loudness(l)) return r;
+    if (n_in > LD_MAX_N) return set_error(GSV_E_ARG, "loudness: more than 640 * 4096 samples");
+    if (n_in > 0 && (!audio_32k || !out)) return set_error(GSV_E_ARG, "null audio buffer");
+    hipSetDevice(eng->device);
+    StreamScope sc(eng, stream);
+    const AudioOutItem a{audio_32k, out, n_in, n_out, rate, out_format, nullptr};
+    return eng->audio_out(&a, &l, 1, gsv_engine::AO_SYNC, sc.st());
 }

@@ -156,6 +156,9 @@ gsv_engine::~gsv_engine() {
     if (ao_pin) hipHostFree(ao_pin);
     for (hipEvent_t e : ao_ev)
         if (e) hipEventDestroy(e);
+    if (lo_pin) hipHostFree(lo_pin);
+    for (hipEvent_t e : lo_ev)
+        if (e) hipEventDestroy(e);
     if (res_pin) hipHostFree(res_pin);
     for (GenSlot& g : gq) {
         if (g.res) hipHostFree(g.res);

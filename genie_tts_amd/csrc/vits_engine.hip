@@ -718,7 +718,7 @@ int gsv_engine::set_vocoder_cus(int K) {
 // The call is queued, not launched: its ~400 launches are issued by the next
 // T2S generate right after the persistent decode kernel (vits_launch_queued), so
 // the host enqueues them while the GPU decodes instead of delaying that T2S.
-int gsv_engine::vits_async(const gsv_vits_item& u, float noise_scale, hipStream_t caller) {
+int gsv_engine::vits_async(const gsv_vits_item& u, const gsv_loudness* norm, float noise_scale, hipStream_t caller) {
     if (!vstream) return set_error(GSV_E_STATE, "overlapped vocoder: set option vocoder_cus first");
     if (int r = vits_wait(nullptr)) return r;
     if (vb_active)
@@ -730,6 +730,7 @@ int gsv_engine::vits_async(const gsv_vits_item& u, float noise_scale, hipStream_
     }
     hipEventRecord(vev_in, caller);   // the inputs are ready in the caller's stream order here
     vcall = u;
+    vcall_norm = norm ? *norm : gsv_loudness{};
     vcall_scale = noise_scale;
     vqueued = true;
     return 0;
@@ -747,7 +748,8 @@ int gsv_engine::vits_launch_queued(hipStream_t s) {
                                  u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0,
                                  vcall_scale, u.audio, s, use_convh ? vovf : nullptr, timing, u.speed))
         return r;
-    if (int r = audio_out_items(&u, 1, AO_ASYNC, s)) return r;   // on the vocoder's stream, behind its pass
+    // on the vocoder's stream, behind its pass
+    if (int r = audio_out_items(&u, vcall_norm.target != 0.f ? &vcall_norm : nullptr, 1, AO_ASYNC, s)) return r;
     if (use_convh) hipMemcpyAsync(vovf_host, vovf, 4, hipMemcpyDeviceToHost, s);
     hipEventRecord(vev_done, s);
     vpending = true;
@@ -771,7 +773,8 @@ int gsv_engine::vits_wait(hipStream_t caller) {
                                      u.noise_mode == 2 ? u.noise_seed : 0, vcall_scale, u.audio, vlast, nullptr,
                                      timing, u.speed))
             return r;
-        if (int r = audio_out_items(&u, 1, AO_ASYNC, vlast)) return r;   // `out` from the re-run's audio
+        // `out` (and its loudness) from the re-run's audio
+        if (int r = audio_out_items(&u, vcall_norm.target != 0.f ? &vcall_norm : nullptr, 1, AO_ASYNC, vlast)) return r;
         hipEventRecord(vev_done, vlast);
         if (hipEventSynchronize(vev_done) != hipSuccess) return set_error(GSV_E_HIP, "overlapped vocoder re-run");
     }
@@ -1164,7 +1167,8 @@ int gsv_engine::vits_front(VitsWorkspace& W, const int64_t* text_seq, int n_text
 // workspace), so up to K vocoder chains -- each a few hundred small launches that
 // under-fill the chip -- overlap on the GPU.  Each utterance has its own overflow
 // flag; after the join, flagged utterances are decoded again on the f32 path.
-int gsv_engine::vits_decode_batch(int n, const gsv_vits_item* it, float noise_scale, hipStream_t s) {
+int gsv_engine::vits_decode_batch(int n, const gsv_vits_item* it, const gsv_loudness* norm, float noise_scale,
+                                  hipStream_t s) {
     if (n <= 0) return 0;
     if (vb_active)   // an overlapped batch shares the lanes: finish it first
         if (int r = vits_batch_finish(nullptr)) return r;
@@ -1176,9 +1180,10 @@ int gsv_engine::vits_decode_batch(int n, const gsv_vits_item* it, float noise_sc
                                 u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0,
                                 noise_scale, u.audio, s, u.speed))
             return r;
-        return audio_out_items(&u, 1, AO_SYNC, s);
+        return audio_out_items(&u, norm, 1, AO_SYNC, s);
     }
     vb_items.assign(it, it + n);
+    vb_norm.assign(norm, norm ? norm + n : norm);
     if (int r = vits_batch_launch(noise_scale, s, true)) return r;
     return vits_batch_finish(s);
 }
@@ -1617,7 +1622,7 @@ int gsv_engine::vits_batch_finish(hipStream_t s) {
     }
     if (hipGetLastError() != hipSuccess) return set_error(GSV_E_HIP, "vocoder batch");
     // the output stage: one launch over the batch's items, behind the re-runs, so from the final audio
-    return audio_out_items(vb_items.data(), n, AO_BATCH_AT, s);
+    return audio_out_items(vb_items.data(), vb_norm.empty() ? nullptr : vb_norm.data(), n, AO_BATCH_AT, s);
 }
 
 // V2: the reference encoder alone (vits(v2)#79-271: ref spectrogram -> MelStyleEncoder ->
@@ -1679,9 +1684,21 @@ static bool vits_item_ok(const gsv_vits_item& u) {
 
 extern "C" int gsv_vits_frames(int32_t n_sem, float speed) { return vits_frames(n_sem, speed); }
 
-extern "C" int gsv_vits_decode_item(gsv_engine* eng, const gsv_vits_item* item, float noise_scale, void* stream) {
+// The loudness specs beside items: each valid, and an item with a target has `out`.
+static int vits_norm_ok(const gsv_vits_item* items, const gsv_loudness* norm, int n) {
+    for (int i = 0; norm && i < n; ++i) {
+        if (int r = check_loudness(norm[i])) return r;
+        if (norm[i].target != 0.f && !items[i].out)
+            return set_error(GSV_E_ARG, "loudness target on an item without `out`");
+    }
+    return 0;
+}
+
+extern "C" int gsv_vits_decode_item_norm(gsv_engine* eng, const gsv_vits_item* item, const gsv_loudness* norm,
+                                         float noise_scale, void* stream) {
     if (!eng) return set_error(GSV_E_ARG, "null engine");
     if (!item || !vits_item_ok(*item)) return set_error(GSV_E_ARG, "bad vocoder item");
+    if (int r = vits_norm_ok(item, norm, 1)) return r;
     hipSetDevice(eng->device);
     if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
     StreamScope sc(eng, stream);
@@ -1690,11 +1707,15 @@ extern "C" int gsv_vits_decode_item(gsv_engine* eng, const gsv_vits_item* item, 
                                  u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0,
                                  noise_scale, u.audio, sc.st(), u.speed))
         return r;
-    return eng->audio_out_items(&u, 1, gsv_engine::AO_SYNC, sc.st());
+    return eng->audio_out_items(&u, norm, 1, gsv_engine::AO_SYNC, sc.st());
 }
 
-extern "C" int gsv_vits_decode_batch(gsv_engine* eng, int32_t n, const gsv_vits_item* items, float noise_scale,
-                                     void* stream) {
+extern "C" int gsv_vits_decode_item(gsv_engine* eng, const gsv_vits_item* item, float noise_scale, void* stream) {
+    return gsv_vits_decode_item_norm(eng, item, nullptr, noise_scale, stream);
+}
+
+extern "C" int gsv_vits_decode_batch_norm(gsv_engine* eng, int32_t n, const gsv_vits_item* items,
+                                          const gsv_loudness* norm, float noise_scale, void* stream) {
     if (!eng) return set_error(GSV_E_ARG, "null engine");
     if (n < 0 || (n > 0 && !items)) return set_error(GSV_E_ARG, "bad args");
     hipSetDevice(eng->device);
@@ -1702,16 +1723,28 @@ extern "C" int gsv_vits_decode_batch(gsv_engine* eng, int32_t n, const gsv_vits_
     for (int i = 0; i < n; ++i)
         if (!vits_item_ok(items[i]))
             return set_error(GSV_E_ARG, "bad vocoder item " + std::to_string(i));
+    if (int r = vits_norm_ok(items, norm, n)) return r;
     StreamScope sc(eng, stream);
-    return eng->vits_decode_batch(n, items, noise_scale, sc.st());
+    return eng->vits_decode_batch(n, items, norm, noise_scale, sc.st());
+}
+
+extern "C" int gsv_vits_decode_batch(gsv_engine* eng, int32_t n, const gsv_vits_item* items, float noise_scale,
+                                     void* stream) {
+    return gsv_vits_decode_batch_norm(eng, n, items, nullptr, noise_scale, stream);
+}
+
+extern "C" int gsv_vits_decode_async_norm(gsv_engine* eng, const gsv_vits_item* item, const gsv_loudness* norm,
+                                          float noise_scale, void* stream) {
+    if (!eng) return set_error(GSV_E_ARG, "null engine");
+    if (!item || !vits_item_ok(*item)) return set_error(GSV_E_ARG, "bad vocoder item");
+    if (int r = vits_norm_ok(item, norm, 1)) return r;
+    hipSetDevice(eng->device);
+    if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
+    return eng->vits_async(*item, norm, noise_scale, (hipStream_t)stream);
 }
 
 extern "C" int gsv_vits_decode_async(gsv_engine* eng, const gsv_vits_item* item, float noise_scale, void* stream) {
-    if (!eng) return set_error(GSV_E_ARG, "null engine");
-    if (!item || !vits_item_ok(*item)) return set_error(GSV_E_ARG, "bad vocoder item");
-    hipSetDevice(eng->device);
-    if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
-    return eng->vits_async(*item, noise_scale, (hipStream_t)stream);
+    return gsv_vits_decode_async_norm(eng, item, nullptr, noise_scale, stream);
 }
 
 extern "C" int gsv_vits_wait(gsv_engine* eng, void* stream) {
@@ -1720,8 +1753,8 @@ extern "C" int gsv_vits_wait(gsv_engine* eng, void* stream) {
     return eng->vits_wait((hipStream_t)stream);
 }
 
-extern "C" int gsv_vits_decode_batch_async(gsv_engine* eng, int32_t n, const gsv_vits_item* items,
-                                           float noise_scale, void* stream) {
+extern "C" int gsv_vits_decode_batch_async_norm(gsv_engine* eng, int32_t n, const gsv_vits_item* items,
+                                                const gsv_loudness* norm, float noise_scale, void* stream) {
     if (!eng) return set_error(GSV_E_ARG, "null engine");
     if (n <= 0 || !items) return set_error(GSV_E_ARG, "bad args");
     hipSetDevice(eng->device);
@@ -1729,12 +1762,19 @@ extern "C" int gsv_vits_decode_batch_async(gsv_engine* eng, int32_t n, const gsv
     for (int i = 0; i < n; ++i)
         if (!vits_item_ok(items[i]))
             return set_error(GSV_E_ARG, "bad vocoder item " + std::to_string(i));
+    if (int r = vits_norm_ok(items, norm, n)) return r;
     if (int r = eng->vits_batch_finish(nullptr)) return r;
     if (int r = eng->vits_wait(nullptr)) return r;
     eng->vb_items.assign(items, items + n);
+    eng->vb_norm.assign(norm, norm ? norm + n : norm);
     // ordered after the caller's stream only: the engine stream stays free for the T2S
     // of the next batch, which runs beside this one
     return eng->vits_batch_launch(noise_scale, (hipStream_t)stream, false);
+}
+
+extern "C" int gsv_vits_decode_batch_async(gsv_engine* eng, int32_t n, const gsv_vits_item* items,
+                                           float noise_scale, void* stream) {
+    return gsv_vits_decode_batch_async_norm(eng, n, items, nullptr, noise_scale, stream);
 }
 
 extern "C" int gsv_vits_batch_wait(gsv_engine* eng, void* stream) {

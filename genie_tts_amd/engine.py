@@ -86,6 +86,11 @@ class VitsItem(ctypes.Structure):
     ]
 
 
+class Loudness(ctypes.Structure):
+    """gsv_loudness: the loudness spec beside a vocoder item (target 0: off for that item)."""
+    _fields_ = [("target", ctypes.c_float), ("peak", ctypes.c_float), ("stats", ctypes.c_void_p)]
+
+
 class Sampler(ctypes.Structure):
     _fields_ = [
         ("top_k", ctypes.c_int32), ("temperature", ctypes.c_float),
@@ -325,6 +330,15 @@ def lib():
         L.gsv_audio_samples.argtypes = [i32, i32]
         L.gsv_audio_convert.argtypes = [vp, vp, i32, i32, i32, vp, vp]
         L.gsv_vits_decode_batch_async.argtypes = [vp, i32, ctypes.POINTER(VitsItem), ctypes.c_float, vp]
+        ldp = ctypes.POINTER(Loudness)
+        L.gsv_loudness_coeffs.argtypes = [i32, ctypes.POINTER(ctypes.c_double)]
+        L.gsv_vits_decode_item_norm.argtypes = [vp, ctypes.POINTER(VitsItem), ldp, ctypes.c_float, vp]
+        L.gsv_vits_decode_batch_norm.argtypes = [vp, i32, ctypes.POINTER(VitsItem), ldp, ctypes.c_float, vp]
+        L.gsv_vits_decode_batch_async_norm.argtypes = [vp, i32, ctypes.POINTER(VitsItem), ldp, ctypes.c_float, vp]
+        L.gsv_vits_decode_async_norm.argtypes = [vp, ctypes.POINTER(VitsItem), ldp, ctypes.c_float, vp]
+        L.gsv_audio_loudness.argtypes = [vp, vp, i32, vp, vp]
+        L.gsv_audio_normalize.argtypes = [vp, vp, i32, ctypes.c_float, ctypes.c_float, i32, i32, vp, vp, vp]
+        L.gsv_debug_loudness_hops.argtypes = [vp, vp, i32, vp, vp]
         L.gsv_vits_batch_wait.argtypes = [vp, vp]
         L.gsv_t2s_prefetch.argtypes = [vp, ctypes.POINTER(Utt), ctypes.POINTER(Sampler), vp]
         L.gsv_t2s_generate_start.argtypes = [vp, ctypes.POINTER(Utt), ctypes.POINTER(Sampler), vp]
@@ -392,6 +406,9 @@ EXPORTED = (
     "gsv_audio_samples", "gsv_audio_convert", "gsv_debug_gemm", "gsv_debug_rows",
     "gsv_debug_conv", "gsv_debug_mrf_pair", "gsv_debug_mha", "gsv_debug_vits_rows",
     "gsv_debug_attn", "gsv_debug_attn_out", "gsv_debug_gemv", "gsv_debug_ffn", "gsv_debug_embed",
+    "gsv_loudness_coeffs", "gsv_vits_decode_item_norm", "gsv_vits_decode_batch_norm",
+    "gsv_vits_decode_batch_async_norm", "gsv_vits_decode_async_norm", "gsv_audio_loudness",
+    "gsv_audio_normalize", "gsv_debug_loudness_hops",
 )
 
 
@@ -468,6 +485,30 @@ def check_out_format(sample_rate=None, pcm16=False) -> dict:
     if pcm16:
         out["pcm16"] = True
     return out
+
+
+def check_loudness(loudness=None, peak=None) -> dict:
+    """The loudness keys of a vocoder call, validated: `loudness` a target in LUFS within
+    [-50, -5], `peak` a linear sample-peak ceiling in (0, 1] (None: -1 dBFS).  ValueError
+    otherwise.  Nothing when loudness is None, and the call is then today's."""
+    out = {}
+    for name, v, lo, hi in (("loudness", loudness, -50.0, -5.0), ("peak", peak, 0.0, 1.0)):
+        if v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or \
+                not math.isfinite(float(v)) or not lo <= float(v) <= hi or (name == "peak" and float(v) == 0.0):
+            raise ValueError(f"loudness must be a target in LUFS within [-50, -5], not {v!r}" if name == "loudness"
+                             else f"peak must be a linear ceiling in (0, 1], not {v!r}")
+        out[name] = float(v)
+    return out if loudness is not None else {}
+
+
+def loudness_coeffs(rate: int):
+    """gsv_loudness_coeffs: the K-weighting biquads at `rate` as float64 [10] (shelf b0 b1 b2 a1
+    a2, high-pass b0 b1 b2 a1 a2).  Host only: needs the library, not a GPU."""
+    out = (ctypes.c_double * 10)()
+    _check(lib().gsv_loudness_coeffs(int(rate), out), "gsv_loudness_coeffs")
+    return np.array(out[:], np.float64)
 
 
 def _torch():
@@ -973,24 +1014,35 @@ class Engine:
 
     def vits_decode(self, text_seq, pred_semantic, ref_audio=None, ge=None, ge_advanced=None,
                     eps=None, noise_scale: float = 0.5, noise_seed: Optional[int] = None, speed: float = 1.0,
-                    sample_rate: Optional[int] = None, pcm16: bool = False):
+                    sample_rate: Optional[int] = None, pcm16: bool = False, loudness: Optional[float] = None,
+                    peak: Optional[float] = None):
         """vits_fp32.onnx for one utterance.  Noise of z_p: eps (tensor/array [192, T']) if
         given, else the engine's Philox N(0,1) stream keyed by noise_seed if given, else zeros.
         speed: the speech rate (0.25 .. 4; T' = vits_frames(G, speed) frames, 640 T' samples).
         sample_rate / pcm16: the output stage (see audio_convert) behind the vocoder, on the GPU;
-        the result is then the converted tensor (the 32 kHz float32 one: self.vits_audio_32k[0])."""
+        the result is then the converted tensor (the 32 kHz float32 one: self.vits_audio_32k[0]).
+        loudness / peak: the result normalised to that target in LUFS under the peak ceiling (see
+        audio_convert), measured and applied on the GPU; its stats: self.vits_loudness[0]."""
         fmt = check_out_format(sample_rate, pcm16)
+        fmt.update(check_loudness(loudness, peak))
         if noise_seed is not None and eps is None:
             return self.vits_decode_batch([dict(text_seq=text_seq, pred_semantic=pred_semantic, ref_audio=ref_audio,
                                                 ge=ge, ge_advanced=ge_advanced, noise_seed=noise_seed,
                                                 speed=speed, **fmt)], noise_scale)[0]
         if float(speed) != 1.0 or fmt:
+            norm = []
             item, keep, audio = self._vits_item(dict(text_seq=text_seq, pred_semantic=pred_semantic,
                                                      ref_audio=ref_audio, ge=ge, ge_advanced=ge_advanced, eps=eps,
-                                                     speed=speed, **fmt))
-            _check(lib().gsv_vits_decode_item(self.h, ctypes.byref(item), ctypes.c_float(noise_scale), _stream()),
-                   "gsv_vits_decode_item")
+                                                     speed=speed, **fmt), norm)
+            if norm[0][0].target:
+                _check(lib().gsv_vits_decode_item_norm(self.h, ctypes.byref(item), ctypes.byref(norm[0][0]),
+                                                       ctypes.c_float(noise_scale), _stream()),
+                       "gsv_vits_decode_item_norm")
+            else:
+                _check(lib().gsv_vits_decode_item(self.h, ctypes.byref(item), ctypes.c_float(noise_scale), _stream()),
+                       "gsv_vits_decode_item")
             self.vits_audio_32k = [keep[-1] if item.out else audio]
+            self.vits_loudness = [norm[0][1]]
             return audio
         t = self.torch
         ts = self._ids(text_seq)
@@ -1007,25 +1059,62 @@ class Engine:
                "gsv_vits_decode")
         return audio
 
-    def audio_convert(self, audio, sample_rate: int = 32000, pcm16: bool = False):
+    def audio_convert(self, audio, sample_rate: int = 32000, pcm16: bool = False, loudness: Optional[float] = None,
+                      peak: Optional[float] = None):
         """The output stage alone (gsv_audio_convert): 32 kHz float32 audio [n] -> its
         audio_samples(n, sample_rate) samples at sample_rate (one of SAMPLE_RATES; the polyphase
         resample of include/genie_engine.h, scipy.signal.resample_poly's default filter), as float32
         or, with pcm16, saturated int16 ((x * 32767).astype(int16), the reference's chunk format).
-        One launch on the GPU; a device tensor."""
+        One launch on the GPU; a device tensor.
+        loudness / peak (gsv_audio_normalize): the audio is first measured by ITU-R BS.1770-4 and
+        every sample multiplied, before the int16 conversion, by the gain that brings it to
+        `loudness` LUFS, limited so that the 32 kHz sample peak stays under `peak` (linear, None:
+        -1 dBFS); self.vits_loudness[0] is then the device stats [loudness, peak, gain, blocks_kept]."""
         t = self.torch
         a = self._dev(audio, t.float32).reshape(-1)
         out = t.empty((audio_samples(a.numel(), sample_rate),), dtype=t.int16 if pcm16 else t.float32, device=self.dev)
+        ld = check_loudness(loudness, peak)
+        if ld:
+            stats = t.empty((4,), dtype=t.float32, device=self.dev)
+            _check(lib().gsv_audio_normalize(self.h, _ptr(a), a.numel(), ctypes.c_float(ld["loudness"]),
+                                             ctypes.c_float(ld.get("peak", 0.0)), int(sample_rate), int(bool(pcm16)),
+                                             _ptr(out), _ptr(stats), _stream()), "gsv_audio_normalize")
+            self.vits_loudness = [stats]
+            return out
         _check(lib().gsv_audio_convert(self.h, _ptr(a), a.numel(), int(sample_rate), int(bool(pcm16)), _ptr(out),
                                        _stream()), "gsv_audio_convert")
         return out
 
-    vits_audio_32k: list = []      # the 32 kHz float32 tensors of the last vocoder call, in item order
+    def audio_loudness(self, audio):
+        """(loudness in LUFS, sample peak) of 32 kHz float32 audio [n], n <= 640 * 4096, by ITU-R
+        BS.1770-4 on the GPU (gsv_audio_loudness); -inf for silence.  self.vits_loudness[0] holds the
+        device stats [loudness, peak, gain (1), blocks_kept]."""
+        t = self.torch
+        a = self._dev(audio, t.float32).reshape(-1)
+        stats = t.empty((4,), dtype=t.float32, device=self.dev)
+        _check(lib().gsv_audio_loudness(self.h, ctypes.c_void_p(a.data_ptr()), a.numel(), _ptr(stats), _stream()),
+               "gsv_audio_loudness")
+        self.vits_loudness = [stats]
+        lufs, pk = stats[:2].cpu().tolist()
+        return lufs, pk
 
-    def _vits_item(self, it: dict):
+    def debug_loudness_hops(self, audio):
+        """gsv_debug_loudness_hops: the K-weighted energy of each full 100 ms hop, device [n // 3200]."""
+        t = self.torch
+        a = self._dev(audio, t.float32).reshape(-1)
+        e = t.empty((a.numel() // 3200,), dtype=t.float32, device=self.dev)
+        _check(lib().gsv_debug_loudness_hops(self.h, ctypes.c_void_p(a.data_ptr()), a.numel(), _ptr(e), _stream()),
+               "gsv_debug_loudness_hops")
+        return e
+
+    vits_audio_32k: list = []      # the 32 kHz float32 tensors of the last vocoder call, in item order
+    vits_loudness: list = []       # its items' loudness stats (device float32 [4]; None: not normalised)
+
+    def _vits_item(self, it: dict, norm: Optional[list] = None):
         """(VitsItem, tensors it points at, result tensor) of one vocoder call.  With the item
-        keys sample_rate / pcm16 the result is the output stage's tensor (the item's `out`), and
-        the 32 kHz float32 audio, still written, is the last of the kept tensors."""
+        keys sample_rate / pcm16 / loudness the result is the output stage's tensor (the item's
+        `out`), and the 32 kHz float32 audio, still written, is the last of the kept tensors.
+        norm: a list that receives the item's (Loudness, stats tensor or None)."""
         t = self.torch
         ts, sem = self._ids(it["text_seq"]), self._ids(it["pred_semantic"])
         G = sem.numel()
@@ -1048,7 +1137,13 @@ class Engine:
                         0 if ga is None else ga.data_ptr(), 0 if e is None else e.data_ptr(),
                         int(seed or 0) & 0xFFFFFFFFFFFFFFFF, mode, audio.data_ptr(), speed)
         fmt = check_out_format(it.get("sample_rate"), it.get("pcm16"))
-        if not fmt:
+        ld = check_loudness(it.get("loudness"), it.get("peak"))
+        stats = t.empty((4,), dtype=t.float32, device=self.dev) if ld else None
+        if norm is not None:
+            norm.append((Loudness(ld["loudness"], ld.get("peak", 0.0), stats.data_ptr()) if ld else Loudness(), stats))
+        elif ld:
+            raise EngineError("loudness on an entry without a loudness spec")
+        if not fmt and not ld:
             return item, [ts, sem, ra, g, ga, e], audio
         rate, pcm = fmt.get("sample_rate", 32000), bool(fmt.get("pcm16"))
         out = t.empty((audio_samples(640 * frames, rate),), dtype=t.int16 if pcm else t.float32, device=self.dev)
@@ -1066,31 +1161,43 @@ class Engine:
         noise_seed, optional speed.  Returns one audio tensor [640 T'] per item (1280 G at speed 1).
         Optional sample_rate / pcm16 per item: that item's result is the output stage's tensor
         (one stage launch for the batch); self.vits_audio_32k then holds every item's 32 kHz audio."""
+        arr, norm, keep, outs, a32 = self._vits_items(items)
+        if norm is not None:
+            _check(lib().gsv_vits_decode_batch_norm(self.h, len(items), arr, norm, ctypes.c_float(noise_scale),
+                                                    _stream()), "gsv_vits_decode_batch_norm")
+        else:
+            _check(lib().gsv_vits_decode_batch(self.h, len(items), arr, ctypes.c_float(noise_scale), _stream()),
+                   "gsv_vits_decode_batch")
+        self.vits_audio_32k = a32
+        return outs
+
+    def _vits_items(self, items: Sequence[dict]):
+        """The item array of a batch, its gsv_loudness array (None when no item has a target: the
+        plain entry is then called), the kept tensors, the results and the 32 kHz tensors."""
         arr = (VitsItem * len(items))()
-        keep, outs, a32 = [], [], []
+        keep, outs, a32, norm = [], [], [], []
         for i, it in enumerate(items):
-            arr[i], k, audio = self._vits_item(it)
+            arr[i], k, audio = self._vits_item(it, norm)
             keep += k
             outs.append(audio)
             a32.append(k[-1] if arr[i].out else audio)
-        _check(lib().gsv_vits_decode_batch(self.h, len(items), arr, ctypes.c_float(noise_scale), _stream()),
-               "gsv_vits_decode_batch")
-        self.vits_audio_32k = a32
-        return outs
+        self.vits_loudness = [st for _, st in norm]
+        if not any(st is not None for st in self.vits_loudness):
+            return arr, None, keep, outs, a32
+        keep += self.vits_loudness
+        return arr, (Loudness * len(items))(*[l for l, _ in norm]), keep, outs, a32
 
     def vits_decode_batch_async(self, items: Sequence[dict], noise_scale: float = 0.5):
         """vits_decode_batch without the join (gsv_vits_decode_batch_async): the lanes run
         beside whatever T2S is issued next.  Returns the audio tensors, valid after
         vits_batch_wait()."""
-        arr = (VitsItem * len(items))()
-        keep, outs, a32 = [], [], []
-        for i, it in enumerate(items):
-            arr[i], k, audio = self._vits_item(it)
-            keep += k
-            outs.append(audio)
-            a32.append(k[-1] if arr[i].out else audio)
-        _check(lib().gsv_vits_decode_batch_async(self.h, len(items), arr, ctypes.c_float(noise_scale),
-                                                 _stream()), "gsv_vits_decode_batch_async")
+        arr, norm, keep, outs, a32 = self._vits_items(items)
+        if norm is not None:
+            _check(lib().gsv_vits_decode_batch_async_norm(self.h, len(items), arr, norm, ctypes.c_float(noise_scale),
+                                                          _stream()), "gsv_vits_decode_batch_async_norm")
+        else:
+            _check(lib().gsv_vits_decode_batch_async(self.h, len(items), arr, ctypes.c_float(noise_scale),
+                                                     _stream()), "gsv_vits_decode_batch_async")
         self.vits_audio_32k = a32
         # items and device buffers live until the wait -- also a previous batch's, which this
         # call only ordered behind the engine stream (its lanes may still read them)
@@ -1114,10 +1221,17 @@ class Engine:
     def vits_decode_async(self, item: dict, noise_scale: float = 0.5):
         """Start one vocoder call on the vocoder CUs (gsv_vits_decode_async) and return its
         audio tensor [640 T'], valid after vits_wait().  item as for vits_decode_batch."""
-        it, keep, audio = self._vits_item(item)
-        _check(lib().gsv_vits_decode_async(self.h, ctypes.byref(it), ctypes.c_float(noise_scale), _stream()),
-               "gsv_vits_decode_async")
-        self._vits_keep = keep   # device inputs stay alive until the call is finished
+        norm = []
+        it, keep, audio = self._vits_item(item, norm)
+        if norm[0][0].target:
+            _check(lib().gsv_vits_decode_async_norm(self.h, ctypes.byref(it), ctypes.byref(norm[0][0]),
+                                                    ctypes.c_float(noise_scale), _stream()),
+                   "gsv_vits_decode_async_norm")
+        else:
+            _check(lib().gsv_vits_decode_async(self.h, ctypes.byref(it), ctypes.c_float(noise_scale), _stream()),
+                   "gsv_vits_decode_async")
+        self._vits_keep = keep + [norm[0][1]]   # device inputs stay alive until the call is finished
+        self.vits_loudness = [norm[0][1]]
         self.vits_audio_32k = [keep[-1] if it.out else audio]
         return audio
 

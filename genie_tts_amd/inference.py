@@ -25,7 +25,7 @@ from typing import Callable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from .engine import EngineStopped, Sampler, check_out_format, request_stop_all, vits_frames
+from .engine import EngineStopped, Sampler, check_loudness, check_out_format, request_stop_all, vits_frames
 from .sessions import (EncoderSession, FirstStageDecoderSession, StageDecoderSession, VitsSession,
                        PromptEncoderSession)
 
@@ -103,13 +103,17 @@ class GENIE:
             stage_decoder, vocoder, prompt_encoder=None, language: str = "japanese",
             text_bert: Optional[np.ndarray] = None, g2p: Optional[Callable] = None,
             sampler: Optional[Sampler] = None, speed: float = 1.0, sample_rate: Optional[int] = None,
-            pcm16: bool = False) -> Optional[np.ndarray]:
+            pcm16: bool = False, loudness: Optional[float] = None,
+            peak: Optional[float] = None) -> Optional[np.ndarray]:
         """speed: the speech rate (0.25 .. 4, GPT-SoVITS's `speed`; 1: the reference's audio).
         sample_rate (one of engine.SAMPLE_RATES) / pcm16: the audio at that rate and / or as int16,
-        converted on the GPU behind the vocoder (Engine.audio_convert); neither: 32 kHz float32."""
+        converted on the GPU behind the vocoder (Engine.audio_convert); neither: 32 kHz float32.
+        loudness (LUFS, -50 .. -5) / peak (linear ceiling, default -1 dBFS): the audio normalised
+        to that BS.1770-4 level on the GPU, in front of the conversion; None: as the vocoder gives it."""
         vits_frames(0, speed)          # ValueError for a bad rate, before any GPU work
         rate = {} if float(speed) == 1.0 else {"speed": float(speed)}
         rate.update(check_out_format(sample_rate, pcm16))   # ValueError for an unsupported sample rate
+        rate.update(check_loudness(loudness, peak))         # ... or a bad loudness target / ceiling
         if isinstance(text, str):
             if g2p is None:
                 raise ValueError("text input needs a g2p(text, language) callable (G2P is outside this engine)")
@@ -141,7 +145,8 @@ class GENIE:
                    first_stage_decoder, stage_decoder, vocoder, prompt_encoder=None, language: str = "japanese",
                    text_bert: Optional[np.ndarray] = None, g2p: Optional[Callable] = None,
                    sampler: Optional[Sampler] = None, vocoder_cus: int = 64, speed: float = 1.0,
-                   sample_rate: Optional[int] = None, pcm16: bool = False):
+                   sample_rate: Optional[int] = None, pcm16: bool = False, loudness: Optional[float] = None,
+                   peak: Optional[float] = None):
         """tts over a list of sentences, yielding each sentence's audio in order (the
         reference runs them one after the other: TTSPlayer._tts_worker_loop,
         Core/TTSPlayer.py:56-107).  Engine-backed sessions pipeline them: sentence i's
@@ -150,9 +155,11 @@ class GENIE:
         those CUs during sentence i's decode (gsv_t2s_prefetch), so sentence i is
         yielded once sentence i+1's T2S is done.  Same tokens and audio as calling
         tts per sentence.  speed: the speech rate of every sentence; sample_rate / pcm16: their
-        output format (as for tts; the stage runs on the vocoder's CUs)."""
+        output format (as for tts; the stage runs on the vocoder's CUs); loudness / peak: every
+        sentence normalised on its own (as for tts), measured on the vocoder's CUs too."""
         vits_frames(0, speed)          # a bad rate fails here, before anything is started
         fmt = check_out_format(sample_rate, pcm16)
+        fmt.update(check_loudness(loudness, peak))
         eng = _engine_of(encoder, first_stage_decoder, stage_decoder, vocoder)
         if eng is None or vocoder_cus <= 0 or len(texts) < 2:
             for t in texts:
@@ -265,7 +272,8 @@ class GENIE:
 
     def tts_batch(self, items: Sequence[tuple], prompt_audio: ReferenceAudio, model, sampler: Sampler,
                   speed: Union[float, Sequence[float]] = 1.0, samplers: Optional[Sequence[Sampler]] = None,
-                  streams: Optional[Sequence[int]] = None, sample_rate=None, pcm16=False) -> List[np.ndarray]:
+                  streams: Optional[Sequence[int]] = None, sample_rate=None, pcm16=False, loudness=None,
+                  peak=None) -> List[np.ndarray]:
         """Batched synthesis for one character and reference: items are
         (text_seq, text_bert|None[, force_steps]).  All sequences decode together
         (one multi-sequence persistent launch, ragged: a finished sequence drops out);
@@ -273,11 +281,14 @@ class GENIE:
         generator once over the whole batch (gsv_vits_decode_batch).  speed: one speech rate
         for all items, or one per item.  samplers / streams: one sampler (and Philox stream) per
         item instead of `sampler`, still one launch (Engine.t2s_generate).  sample_rate / pcm16:
-        the output format, one value for all items or one per item (tts_batch_vocoder)."""
+        the output format, one value for all items or one per item (tts_batch_vocoder); loudness /
+        peak: the loudness target and ceiling, likewise."""
         toks = (self.tts_batch_t2s(items, prompt_audio, model, sampler) if samplers is None and streams is None
                 else self.tts_batch_t2s(items, prompt_audio, model, sampler, samplers=samplers, streams=streams))
         fmt = {} if sample_rate is None and np.ndim(pcm16) == 0 and not pcm16 else dict(sample_rate=sample_rate,
                                                                                          pcm16=pcm16)
+        if loudness is not None:
+            fmt.update(loudness=loudness, peak=peak)
         wavs = self.tts_batch_vocoder(items, toks, prompt_audio, model, speed=speed, **fmt)
         return [w if isinstance(w, np.ndarray) else w.cpu().numpy() for w in wavs]
 
@@ -297,13 +308,15 @@ class GENIE:
 
     def tts_batch_vocoder(self, items: Sequence[tuple], toks, prompt_audio: ReferenceAudio, model,
                           overlapped: bool = False, speed: Union[float, Sequence[float]] = 1.0,
-                          sample_rate=None, pcm16=False):
+                          sample_rate=None, pcm16=False, loudness=None, peak=None):
         """The vocoder half of tts_batch.  overlapped=True (engine-backed vocoder only) starts
         the batch on the vocoder lanes and returns device tensors that are valid after
         model.ENGINE.vits_batch_wait(); the T2S of the next batch runs beside it
         (gsv_vits_decode_batch_async).  sample_rate (None: 32 kHz float32 as ever) / pcm16: the
         output format, one value or one per item; a batch may mix rates, and the whole batch is
-        converted by one launch of the engine's output stage."""
+        converted by one launch of the engine's output stage.  loudness / peak (None: off): a target
+        in LUFS and a peak ceiling, one value or one per item (None entries: that item as ever); the
+        items with a target are measured in one pass and their gains applied by that same launch."""
         eng = model.ENGINE
         speeds = [float(speed)] * len(items) if np.ndim(speed) == 0 else [float(v) for v in speed]
         if len(speeds) != len(items):
@@ -314,7 +327,12 @@ class GENIE:
         pcms = [bool(pcm16)] * len(items) if np.ndim(pcm16) == 0 else [bool(v) for v in pcm16]
         if len(rates) != len(items) or len(pcms) != len(items):
             raise ValueError("sample_rate / pcm16: one value, or one per item")
+        louds = [loudness] * len(items) if loudness is None or np.ndim(loudness) == 0 else list(loudness)
+        peaks = [peak] * len(items) if peak is None or np.ndim(peak) == 0 else list(peak)
+        if len(louds) != len(items) or len(peaks) != len(items):
+            raise ValueError("loudness / peak: one value, or one per item")
         fmts = [check_out_format(r, p) for r, p in zip(rates, pcms)]   # ValueError for an unsupported rate
+        fmts = [dict(f, **check_loudness(l, k)) for f, l, k in zip(fmts, louds, peaks)]
         if model.PROMPT_ENCODER is not None:
             prompt_audio.update_global_emb(model.PROMPT_ENCODER)
         cond = ({"ref_audio": prompt_audio.audio_32k} if model.PROMPT_ENCODER is None else

@@ -11,7 +11,9 @@ CPU ONNX session set, and uvicorn `workers > 1` cannot share its globals).
                                           the reference's TTSPlayer chunk callback
                                           (Server.py:122-143, TTSPlayer.py:98-107);
                                           with `sample_rate` in the payload the chunks are the
-                                          GPU's int16 samples at that rate (X-Sample-Rate)
+                                          GPU's int16 samples at that rate (X-Sample-Rate);
+                                          with `loudness` (LUFS) / `peak` each sentence is
+                                          normalised on the GPU first (X-Loudness)
   POST /stop                          -> every worker
 
 A worker is a spawned process with HIP_VISIBLE_DEVICES set before anything touches
@@ -60,8 +62,8 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
     import numpy as np
     import genie_tts_amd as genie
     from genie_tts_amd import api, audio as A
-    from genie_tts_amd.engine import (SAMPLING_FIELDS, audio_samples, check_sampling, make_sampler, override_sampler,
-                                      sampler_key, vits_frames)
+    from genie_tts_amd.engine import (SAMPLING_FIELDS, audio_samples, check_loudness, check_sampling, make_sampler,
+                                      override_sampler, sampler_key, vits_frames)
     from genie_tts_amd.inference import tts_client
     from genie_tts_amd.model_manager import model_manager
     from genie_tts_amd.text_splitter import TextSplitter
@@ -139,6 +141,12 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
         r = {"id": msg["id"], "character_name": msg["character_name"], "sentences": sents, "next": 0,
              "force_steps": int(msg.get("force_steps") or 0), "save_path": msg.get("save_path"),
              "chunks": [], "speed": speed, "sampling": sampling, "sampler": None, "sample_rate": out_rate}
+        if "loudness" in msg or "peak" in msg:   # a request without them is accepted exactly as before
+            try:                      # likewise a loudness target or peak ceiling out of range
+                r.update(check_loudness(msg["loudness"] if "loudness" in msg else None, msg.get("peak")))
+            except (TypeError, ValueError) as e:
+                reply(kind="error", id=msg["id"], detail=f"loudness: {e}")
+                return
         resolve_sampler(r, model_manager.get(r["character_name"]))
         pending.append(r)
 
@@ -250,6 +258,8 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
             out_rates = [r["sample_rate"] for r in group]
             if any(v is not None for v in out_rates):   # a round mixes rates: each item its own, as int16
                 rate.update(sample_rate=out_rates, pcm16=[v is not None for v in out_rates])
+            if any("loudness" in r for r in group):     # ... and requests with and without a loudness target
+                rate.update(loudness=[r.get("loudness") for r in group], peak=[r.get("peak") for r in group])
             wavs = tts_client.tts_batch_vocoder(items, toks, ref, m, overlapped=overlapped, **rate)
         except Exception as e:       # noqa: BLE001
             finish_inflight()
@@ -496,6 +506,11 @@ def create_app(router: Router):
         # output sample rate: the stream is then the GPU's int16 samples at that rate (header
         # X-Sample-Rate); absent: 32 kHz, converted on the host as ever
         sample_rate: Optional[Literal[8000, 16000, 22050, 24000, 32000, 44100, 48000]] = None
+        # loudness normalisation on the GPU: a target in LUFS (-50 .. -5, ITU-R BS.1770-4) and a
+        # linear sample-peak ceiling in (0, 1] (absent: -1 dBFS); a value out of range is a 400.
+        # Header X-Loudness; absent: the level the voice has, as ever
+        loudness: Optional[float] = None
+        peak: Optional[float] = None
 
     def check(res: List[dict]) -> None:
         bad = [r for r in res if r["kind"] == "error"]
@@ -526,13 +541,19 @@ def create_app(router: Router):
 
     @app.post("/tts")
     async def tts_endpoint(payload: TTSPayload):
+        try:
+            from .engine import check_loudness
+            check_loudness(payload.loudness, payload.peak)
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"loudness: {e}")
         gen = router.tts(character_name=payload.character_name, text=payload.text,
                          split_sentence=payload.split_sentence, save_path=payload.save_path,
                          force_steps=payload.force_steps, speed=payload.speed,
                          **{k: v for k, v in (("top_k", payload.top_k), ("top_p", payload.top_p),
                                               ("temperature", payload.temperature),
                                               ("repetition_penalty", payload.repetition_penalty),
-                                              ("seed", payload.seed), ("sample_rate", payload.sample_rate))
+                                              ("seed", payload.seed), ("sample_rate", payload.sample_rate),
+                                              ("loudness", payload.loudness), ("peak", payload.peak))
                             if v is not None})
         try:    # surface "not found" as 404 before the stream starts, as the reference does
             first = await gen.__anext__()
@@ -540,7 +561,7 @@ def create_app(router: Router):
             first = None
         except RuntimeError as e:
             code = (404 if "not found" in str(e) else
-                    400 if str(e).startswith(("speed:", "sampling:", "sample_rate:")) else 500)
+                    400 if str(e).startswith(("speed:", "sampling:", "sample_rate:", "loudness:")) else 500)
             raise HTTPException(status_code=code, detail=str(e))
 
         async def body():
@@ -548,7 +569,10 @@ def create_app(router: Router):
                 yield first
                 async for c in gen:
                     yield c
-        headers = None if payload.sample_rate is None else {"X-Sample-Rate": str(payload.sample_rate)}
+        headers = {} if payload.sample_rate is None else {"X-Sample-Rate": str(payload.sample_rate)}
+        if payload.loudness is not None:
+            headers["X-Loudness"] = f"{float(payload.loudness):g}"
+        headers = headers or None
         return StreamingResponse(body(), media_type="audio/wav", headers=headers)
 
     @app.post("/stop")

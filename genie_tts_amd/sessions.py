@@ -181,7 +181,10 @@ class VitsSession(_Session):
 
     Output format: optional "sample_rate" (one of engine.SAMPLE_RATES) and "pcm16" feed entries
     run the engine's output stage behind the vocoder (Engine.audio_convert): the audio is then
-    engine.audio_samples(640 T', sample_rate) samples, float32 or int16."""
+    engine.audio_samples(640 T', sample_rate) samples, float32 or int16.  Optional "loudness" (a
+    target in LUFS, -50 .. -5) and "peak" (a linear ceiling in (0, 1], default -1 dBFS) entries have
+    the audio measured by ITU-R BS.1770-4 and brought to that level on the GPU, in front of the
+    conversion (Engine.audio_convert); the 32 kHz float32 audio is still written unnormalised."""
     OUTPUTS = (NodeArg("audio", ("1280*G",), "tensor(float)"),)
 
     def __init__(self, engine, version: str, noise_scale: float = 0.5, eps_fn=None, noise: str = "philox",
@@ -245,7 +248,8 @@ class VitsSession(_Session):
         else:
             self._need(f, "ge", "ge_advanced")
             cond = dict(ge=f["ge"], ge_advanced=f["ge_advanced"])
-        fmt = {k: f[k] for k in ("sample_rate", "pcm16") if f.get(k) is not None}   # none given: today's call
+        # none given: today's call
+        fmt = {k: f[k] for k in ("sample_rate", "pcm16", "loudness", "peak") if f.get(k) is not None}
         audio = self.engine.vits_decode(f["text_seq"], sem, eps=eps, noise_scale=self.noise_scale, noise_seed=seed,
                                         speed=speed, **cond, **fmt)
         return self._select(output_names, {"audio": _np(audio)})

@@ -333,6 +333,66 @@ int gsv_vits_batch_wait(gsv_engine* eng, void* stream);
 int gsv_vits_decode_async(gsv_engine* eng, const gsv_vits_item* item, float noise_scale, void* stream);
 int gsv_vits_wait(gsv_engine* eng, void* stream);
 
+/* Loudness normalisation (the reference and GPT-SoVITS only clip, so voices differ by several dB;
+ * a caller who wants one level runs a normaliser over the PCM on the host).  The engine measures
+ * an item's final 32 kHz float32 audio by ITU-R BS.1770-4 (mono, channel weight 1) and the output
+ * stage applies the gain to a target under a sample-peak ceiling (EBU R 128), all on the GPU.
+ *   K-weighting: two biquads at 32 kHz.  gsv_loudness_coeffs gives them for any rate, in double:
+ *   shelf  f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196, K = tan(pi f0 / fs),
+ *          Vh = 10^(G/20), Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2,
+ *          b = [(Vh + Vb K/Q + K^2)/a0, 2 (K^2 - Vh)/a0, (Vh - Vb K/Q + K^2)/a0],
+ *          a = [1, 2 (K^2 - 1)/a0, (1 - K/Q + K^2)/a0];
+ *   high-pass f0 = 38.13547087602444, Q = 0.5003270373238773, b = [1, -2, 1],
+ *          a = [1, 2 (K^2 - 1)/(1 + K/Q + K^2), (1 - K/Q + K^2)/(1 + K/Q + K^2)]
+ *   (at 48000 the standard's table).  The engine rounds them to float32 and runs the recurrence
+ *   and the squares in float32 over the whole signal: the impulse response is not truncated.
+ *   Hop energies: e_j = sum of the squared filtered samples over [3200 j, 3200 (j + 1)) (100 ms).
+ *   A gating block is 4 hops, z_j = (e_j + .. + e_{j+3}) / 12800, j = 0 .. n/3200 - 4 (400 ms,
+ *   75 % overlap); samples after the last full block are not measured.
+ *   Gating: l_j = -0.691 + 10 log10 z_j; G = -0.691 + 10 log10(mean z over l_j > -70) - 10; the
+ *   loudness is -0.691 + 10 log10(mean z over l_j > -70 and l_j > G), blocks_kept their count.
+ *   n < 12800: one ungated block over all n samples, its loudness reported; it counts as kept
+ *   when above -70.  No block kept, or n == 0: gain 1, blocks_kept 0 (and, with full blocks or
+ *   n == 0, loudness -inf).
+ *   peak = max |audio|.  gain = min(10^((target - loudness) / 20), ceiling / peak) (the first term
+ *   when peak == 0), from the float32 loudness and peak, written as float32 on the device: no host
+ *   round trip lies between the measurement and the stage that applies it.
+ *   stats = {loudness_lufs, peak, gain, blocks_kept} (device float[4]).  Every sum has one order
+ *   whatever the launch: an item gives the same bits alone, in a batch and on the vocoder stream.
+ *   Applying: y = chain * gain, one rounded float32 multiply after the output stage's fma chain (or
+ *   after the copy at 32000), then the conversion above.  `audio` stays unnormalised.
+ * gsv_loudness rides beside an item (gsv_vits_item cannot grow): target LUFS, 0 == off for this
+ * item, valid -50 <= target <= -5 else GSV_E_ARG; peak: linear ceiling in (0, 1], 0 == 10^(-1/20)
+ * (-1 dBFS, EBU R 128); stats: device float[4] or NULL.  An item with target != 0 needs `out`
+ * (out_rate 0 / out_format 0: a normalised 32 kHz float32 copy), else GSV_E_ARG before any launch;
+ * the signal is at most 640 * 4096 samples. */
+typedef struct { float target; float peak; float* stats; } gsv_loudness;
+/* out = shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2 at `rate`.  Pure: needs no device. */
+int gsv_loudness_coeffs(int32_t rate, double* out /* [10] */);
+/* The `_norm` twins of the entries that take items: norm is [n] (one per item; NULL: the plain
+ * call, which these are then bit for bit, launch for launch).  A batch is one measurement pass
+ * plus one stage launch per 256 items; after an fp16-range re-run the re-run's audio is measured;
+ * under gsv_vits_decode_async_norm both run on the vocoder's stream.  norm is copied: it need
+ * not outlive the call (the stats buffers must, until the wait). */
+int gsv_vits_decode_item_norm(gsv_engine* eng, const gsv_vits_item* item, const gsv_loudness* norm,
+                              float noise_scale, void* stream);
+int gsv_vits_decode_batch_norm(gsv_engine* eng, int32_t n, const gsv_vits_item* items, const gsv_loudness* norm,
+                               float noise_scale, void* stream);
+int gsv_vits_decode_batch_async_norm(gsv_engine* eng, int32_t n, const gsv_vits_item* items,
+                                     const gsv_loudness* norm, float noise_scale, void* stream);
+int gsv_vits_decode_async_norm(gsv_engine* eng, const gsv_vits_item* item, const gsv_loudness* norm,
+                               float noise_scale, void* stream);
+/* The measurement alone: audio_32k (device f32 [n], n <= 640 * 4096) -> stats (device float[4],
+ * gain 1), stream-ordered. */
+int gsv_audio_loudness(gsv_engine* eng, const float* audio_32k, int32_t n, float* stats, void* stream);
+/* Measure and convert: gsv_audio_convert with the gain to `target` (as gsv_loudness: -50 .. -5;
+ * peak 0 == -1 dBFS) applied; stats device float[4] or NULL.  Stream-ordered. */
+int gsv_audio_normalize(gsv_engine* eng, const float* audio_32k, int32_t n_in, float target, float peak,
+                        int32_t out_rate, int32_t out_format, void* out, float* stats, void* stream);
+/* Debug: the hop energies e[n / 3200] of audio (device f32 [n]) alone, so the filter and its carry
+ * can be tested apart from the gate. */
+int gsv_debug_loudness_hops(gsv_engine* eng, const float* audio, int32_t n, float* e, void* stream);
+
 /* The T2S side of the same pipeline: encode + prefill the NEXT sentence ahead, on
  * the vocoder CUs while the current sentence decodes (the reference's per-sentence
  * encoder + first-stage decoder, Inference.py:63-72, moved off the critical path).
