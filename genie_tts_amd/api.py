@@ -38,6 +38,7 @@ from typing import AsyncIterator, Callable, Dict, List, Optional, Sequence, Unio
 import numpy as np
 
 from . import audio as A
+from .engine import vocoder_options
 from .inference import ReferenceAudio, tts_client
 from .model_manager import model_manager
 from .text_splitter import TextSplitter
@@ -233,30 +234,6 @@ def _ensure_sv_emb(m, ref) -> None:
         ref.sv_emb = np.asarray(sv, np.float32).reshape(1, -1)
 
 
-def _rate(speed) -> dict:
-    """The speech-rate keyword of a synthesis call: nothing at 1.0 (today's call, unchanged),
-    ValueError for a rate the engine rejects (outside 0.25 .. 4, not finite)."""
-    from .engine import vits_frames
-    vits_frames(0, speed)
-    return {} if float(speed) == 1.0 else {"speed": float(speed)}
-
-
-def _out_rate(sample_rate, pcm16: bool = False) -> dict:
-    """The output-format keywords of a synthesis call: nothing when sample_rate is None (today's
-    call, unchanged), ValueError for a rate the engine's output stage does not have."""
-    if sample_rate is None:
-        return {}
-    from .engine import check_out_format
-    return check_out_format(sample_rate, pcm16)
-
-
-def _loudness(loudness, peak) -> dict:
-    """The loudness keywords of a synthesis call: nothing when loudness is None (today's call,
-    unchanged), ValueError for a target outside -50 .. -5 LUFS or a ceiling outside (0, 1]."""
-    from .engine import check_loudness
-    return check_loudness(loudness, peak)
-
-
 def _sampling(top_k=None, top_p=None, temperature=None, repetition_penalty=None, seed=None) -> dict:
     """The sampling keywords of a synthesis call that were given, validated (ValueError for
     a value the engine rejects) before anything is synthesized."""
@@ -279,8 +256,8 @@ def _resolve_sampler(character_name: str, sampler, fields: dict):
     return override_sampler(sampler, **fields)
 
 
-def _synthesize(character_name: str, sentence, text_bert=None, sampler=None, speed: float = 1.0,
-                **fmt) -> np.ndarray:
+def _synthesize(character_name: str, sentence, text_bert=None, sampler=None, **opts) -> np.ndarray:
+    """One sentence; opts: the call's engine.vocoder_options."""
     m = model_manager.get(character_name)
     if m is None:
         raise ValueError(f"character '{character_name}' is not loaded")
@@ -294,15 +271,14 @@ def _synthesize(character_name: str, sentence, text_bert=None, sampler=None, spe
         return None
     return tts_client.tts(sentence, ref, m.T2S_ENCODER, m.T2S_FIRST_STAGE_DECODER, m.T2S_STAGE_DECODER, m.VITS,
                           m.PROMPT_ENCODER, m.LANGUAGE, text_bert=text_bert, g2p=_g2p, sampler=sampler,
-                          **_rate(speed), **fmt)
+                          **opts)
 
 
-def _synthesize_all(character_name: str, sentences: List, text_bert=None, sampler=None, speed: float = 1.0,
-                    **fmt):
+def _synthesize_all(character_name: str, sentences: List, text_bert=None, sampler=None, **opts):
     """Every sentence, in order; on the engine the vocoder of one sentence overlaps the
     T2S of the next (GENIE.tts_stream)."""
     if len(sentences) < 2:
-        return [_synthesize(character_name, s, text_bert, sampler, **_rate(speed), **fmt) for s in sentences]
+        return [_synthesize(character_name, s, text_bert, sampler, **opts) for s in sentences]
     m = model_manager.get(character_name)
     if m is None:
         raise ValueError(f"character '{character_name}' is not loaded")
@@ -316,7 +292,7 @@ def _synthesize_all(character_name: str, sentences: List, text_bert=None, sample
         return []
     return list(tts_client.tts_stream(sentences, ref, m.T2S_ENCODER, m.T2S_FIRST_STAGE_DECODER, m.T2S_STAGE_DECODER,
                                       m.VITS, m.PROMPT_ENCODER, m.LANGUAGE, text_bert=text_bert, g2p=_g2p,
-                                      sampler=sampler, vocoder_cus=VOCODER_CUS, **_rate(speed), **fmt))
+                                      sampler=sampler, vocoder_cus=VOCODER_CUS, **opts))
 
 
 def _play(audio: np.ndarray, sample_rate: int = SAMPLE_RATE) -> None:
@@ -350,22 +326,13 @@ def tts(character_name: str, text: Union[str, Sequence[int], np.ndarray], play: 
         peak: Optional[float] = None) -> Optional[np.ndarray]:
     """Internal.py:265-310 (TTSPlayer session: split, synthesize each sentence, save the
     concatenation as 16-bit WAV).  Returns the audio f32 [sum 1280*G_i] at 32 kHz.
-    sample_rate: 8000, 16000, 22050, 24000, 32000, 44100 or 48000 (ValueError otherwise): the audio
-    is returned, saved (the WAV header carries the rate) and played at that rate, each sentence
-    resampled on the GPU behind its vocoder (Engine.audio_convert); None: 32 kHz, today's path.
-    loudness: a target in LUFS (-50 .. -5; ITU-R BS.1770-4 gated loudness, e.g. -16 for speech or
-    EBU R 128's -23): every sentence is measured on the GPU behind its vocoder and scaled to it,
-    in front of the rate conversion, the gain limited so that the sample peak stays under `peak`
-    (linear, (0, 1]; None: -1 dBFS).  With loudness alone the audio is float32 at 32 kHz,
-    normalised; None: the level the voice happens to have, today's path.  ValueError for a bad value.
-    speed: the speech rate (GPT-SoVITS's `speed`, 0.25 .. 4; ValueError otherwise): sentence i
-    is 640 * Engine.vits_frames(G_i, speed) samples, its pitch unchanged.
+    speed, sample_rate, loudness / peak: engine.vocoder_options, per sentence (ValueError for a
+    bad value, before anything is synthesized).  The audio is returned, saved (the WAV header
+    carries the rate) and played at sample_rate, as float32.
     top_k (1..64), top_p (0 < p <= 1, nucleus sampling), temperature (> 0), repetition_penalty
     (> 0), seed: GPT-SoVITS's sampling controls; None keeps the field of `sampler` (or, without
     one, of the character's sampler), a value overrides it on a copy.  ValueError for a bad value."""
-    rate = _rate(speed)
-    rate.update(_out_rate(sample_rate))
-    rate.update(_loudness(loudness, peak))
+    opts = vocoder_options(speed, sample_rate, False, loudness, peak)
     out_rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
     fields = _sampling(top_k, top_p, temperature, repetition_penalty, seed)
     if character_name not in _reference_audios:
@@ -374,7 +341,7 @@ def tts(character_name: str, text: Union[str, Sequence[int], np.ndarray], play: 
     sampler = _resolve_sampler(character_name, sampler, fields)
     _session_stop.clear()                    # TTSPlayer.start_session
     chunks = [c for c in _synthesize_all(character_name, _sentences(text, split_sentence), text_bert, sampler,
-                                         **rate)
+                                         **opts)
               if c is not None]
     audio = np.concatenate(chunks) if chunks else np.zeros(0, np.float32)
     if _session_stop.is_set():               # stopped: the session's STREAM_END (and its save) never runs
@@ -394,13 +361,10 @@ async def tts_async(character_name: str, text: str, play: bool = False, split_se
                     loudness: Optional[float] = None, peak: Optional[float] = None) -> AsyncIterator[bytes]:
     """Internal.py:193-262: yields one raw 16-bit PCM chunk per sentence as soon as it
     is synthesized (TTSPlayer chunk callback), the engine running off the event loop.
-    speed, sampler and the sampling keywords: as for tts.  sample_rate (as for tts): the chunks
-    are the int16 samples at that rate as the GPU's output stage wrote them (32000 gives the
-    bytes of the call without it); None: today's path, converted on the host.  loudness / peak (as
-    for tts): each chunk normalised on the GPU in front of that conversion."""
-    rate = _rate(speed)
-    rate.update(_out_rate(sample_rate, pcm16=True))
-    rate.update(_loudness(loudness, peak))
+    speed, sampler, the sampling keywords, sample_rate and loudness / peak: as for tts.  With a
+    sample_rate the chunks are the int16 samples at that rate as the GPU's output stage wrote
+    them (32000 gives the bytes of the call without it); None: converted on the host."""
+    opts = vocoder_options(speed, sample_rate, sample_rate is not None, loudness, peak)
     out_rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
     fields = _sampling(top_k, top_p, temperature, repetition_penalty, seed)
     if character_name not in _reference_audios:
@@ -413,7 +377,7 @@ async def tts_async(character_name: str, text: str, play: bool = False, split_se
         if _session_stop.is_set():
             return
         audio = await loop.run_in_executor(None, functools.partial(_synthesize, character_name, s, sampler=sampler,
-                                                                     **rate))
+                                                                     **opts))
         if _session_stop.is_set():
             # stop() during the sentence: the reference's worker sends chunk_callback(None) and
             # the iterator ends without that chunk (TTSPlayer.py:109-114, Internal.py:258-262)

@@ -212,32 +212,32 @@ extern "C" int gsv_audio_samples(int32_t n_in, int32_t out_rate) {
     return n < 0 || n > INT32_MAX ? GSV_E_ARG : (int)n;
 }
 
-extern "C" int gsv_audio_convert(gsv_engine* eng, const float* audio_32k, int32_t n_in, int32_t out_rate,
-                                 int32_t out_format, void* out, void* stream) {
+// The output stage alone on one buffer, its arguments checked first; l: null, or the target to bring it to.
+static int audio_entry(gsv_engine* eng, const float* audio_32k, int32_t n_in, const gsv_loudness* l, int32_t out_rate,
+                       int32_t out_format, void* out, void* stream) {
     if (!eng) return set_error(GSV_E_ARG, "null engine");
     const int rate = audio_rate_index(out_rate), n_out = gsv_audio_samples(n_in, out_rate);
     if (rate < 0 || n_out < 0) return set_error(GSV_E_ARG, "out_rate: 8000, 16000, 22050, 24000, 32000, 44100 or 48000");
     if (out_format < 0 || out_format > 1) return set_error(GSV_E_ARG, "out_format: 0 (float32) or 1 (int16)");
+    if (l) {
+        if (l->target == 0.f) return set_error(GSV_E_ARG, "loudness target: -50 .. -5 LUFS");
+        if (int r = check_loudness(*l)) return r;
+        if (n_in > LD_MAX_N) return set_error(GSV_E_ARG, "loudness: more than 640 * 4096 samples");
+    }
     if (n_in > 0 && (!audio_32k || !out)) return set_error(GSV_E_ARG, "null audio buffer");
     hipSetDevice(eng->device);
     StreamScope sc(eng, stream);
     const AudioOutItem a{audio_32k, out, n_in, n_out, rate, out_format, nullptr};
-    return eng->audio_out(&a, nullptr, 1, gsv_engine::AO_SYNC, sc.st());
+    return eng->audio_out(&a, l, 1, gsv_engine::AO_SYNC, sc.st());
+}
+
+extern "C" int gsv_audio_convert(gsv_engine* eng, const float* audio_32k, int32_t n_in, int32_t out_rate,
+                                 int32_t out_format, void* out, void* stream) {
+    return audio_entry(eng, audio_32k, n_in, nullptr, out_rate, out_format, out, stream);
 }
 
 extern "C" int gsv_audio_normalize(gsv_engine* eng, const float* audio_32k, int32_t n_in, float target, float peak,
                                    int32_t out_rate, int32_t out_format, void* out, float* stats, void* stream) {
-    if (!eng) return set_error(GSV_E_ARG, "null engine");
-    const int rate = audio_rate_index(out_rate), n_out = gsv_audio_samples(n_in, out_rate);
-    if (rate < 0 || n_out < 0) return set_error(GSV_E_ARG, "out_rate: 8000, 16000, 22050, 24000, 32000, 44100 or 48000");
-    if (out_format < 0 || out_format > 1) return set_error(GSV_E_ARG, "out_format: 0 (float32) or 1 (int16)");
     const gsv_loudness l{target, peak, stats};
-    if (target == 0.f) return set_error(GSV_E_ARG, "loudness target: -50 .. -5 LUFS");
-    if (int r = check_loudness(l)) return r;
-    if (n_in > LD_MAX_N) return set_error(GSV_E_ARG, "loudness: more than 640 * 4096 samples");
-    if (n_in > 0 && (!audio_32k || !out)) return set_error(GSV_E_ARG, "null audio buffer");
-    hipSetDevice(eng->device);
-    StreamScope sc(eng, stream);
-    const AudioOutItem a{audio_32k, out, n_in, n_out, rate, out_format, nullptr};
-    return eng->audio_out(&a, &l, 1, gsv_engine::AO_SYNC, sc.st());
+    return audio_entry(eng, audio_32k, n_in, &l, out_rate, out_format, out, stream);
 }

@@ -1694,13 +1694,29 @@ static int vits_norm_ok(const gsv_vits_item* items, const gsv_loudness* norm, in
     return 0;
 }
 
-extern "C" int gsv_vits_decode_item_norm(gsv_engine* eng, const gsv_vits_item* item, const gsv_loudness* norm,
-                                         float noise_scale, void* stream) {
+// What the four vocoder entries check before anything runs.  one: a single item, checked before
+// the engine's state; else a batch of at least min_n, checked after it, its errors naming the item.
+static int vits_entry_ok(gsv_engine* eng, const gsv_vits_item* items, const gsv_loudness* norm, int n, bool one,
+                         int min_n = 0) {
     if (!eng) return set_error(GSV_E_ARG, "null engine");
-    if (!item || !vits_item_ok(*item)) return set_error(GSV_E_ARG, "bad vocoder item");
-    if (int r = vits_norm_ok(item, norm, 1)) return r;
+    auto args = [&]() -> int {
+        if (one && !items) return set_error(GSV_E_ARG, "bad vocoder item");
+        for (int i = 0; i < n; ++i)
+            if (!vits_item_ok(items[i]))
+                return set_error(GSV_E_ARG, one ? "bad vocoder item" : "bad vocoder item " + std::to_string(i));
+        return vits_norm_ok(items, norm, n);
+    };
+    if (!one && (n < min_n || (n > 0 && !items))) return set_error(GSV_E_ARG, "bad args");
+    if (one)
+        if (int r = args()) return r;
     hipSetDevice(eng->device);
     if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
+    return one ? 0 : args();
+}
+
+extern "C" int gsv_vits_decode_item_norm(gsv_engine* eng, const gsv_vits_item* item, const gsv_loudness* norm,
+                                         float noise_scale, void* stream) {
+    if (int r = vits_entry_ok(eng, item, norm, 1, true)) return r;
     StreamScope sc(eng, stream);
     const gsv_vits_item& u = *item;
     if (int r = eng->vits_decode(u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge, u.ge_adv,
@@ -1716,14 +1732,7 @@ extern "C" int gsv_vits_decode_item(gsv_engine* eng, const gsv_vits_item* item, 
 
 extern "C" int gsv_vits_decode_batch_norm(gsv_engine* eng, int32_t n, const gsv_vits_item* items,
                                           const gsv_loudness* norm, float noise_scale, void* stream) {
-    if (!eng) return set_error(GSV_E_ARG, "null engine");
-    if (n < 0 || (n > 0 && !items)) return set_error(GSV_E_ARG, "bad args");
-    hipSetDevice(eng->device);
-    if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
-    for (int i = 0; i < n; ++i)
-        if (!vits_item_ok(items[i]))
-            return set_error(GSV_E_ARG, "bad vocoder item " + std::to_string(i));
-    if (int r = vits_norm_ok(items, norm, n)) return r;
+    if (int r = vits_entry_ok(eng, items, norm, n, false)) return r;
     StreamScope sc(eng, stream);
     return eng->vits_decode_batch(n, items, norm, noise_scale, sc.st());
 }
@@ -1735,11 +1744,7 @@ extern "C" int gsv_vits_decode_batch(gsv_engine* eng, int32_t n, const gsv_vits_
 
 extern "C" int gsv_vits_decode_async_norm(gsv_engine* eng, const gsv_vits_item* item, const gsv_loudness* norm,
                                           float noise_scale, void* stream) {
-    if (!eng) return set_error(GSV_E_ARG, "null engine");
-    if (!item || !vits_item_ok(*item)) return set_error(GSV_E_ARG, "bad vocoder item");
-    if (int r = vits_norm_ok(item, norm, 1)) return r;
-    hipSetDevice(eng->device);
-    if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
+    if (int r = vits_entry_ok(eng, item, norm, 1, true)) return r;
     return eng->vits_async(*item, norm, noise_scale, (hipStream_t)stream);
 }
 
@@ -1755,14 +1760,7 @@ extern "C" int gsv_vits_wait(gsv_engine* eng, void* stream) {
 
 extern "C" int gsv_vits_decode_batch_async_norm(gsv_engine* eng, int32_t n, const gsv_vits_item* items,
                                                 const gsv_loudness* norm, float noise_scale, void* stream) {
-    if (!eng) return set_error(GSV_E_ARG, "null engine");
-    if (n <= 0 || !items) return set_error(GSV_E_ARG, "bad args");
-    hipSetDevice(eng->device);
-    if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
-    for (int i = 0; i < n; ++i)
-        if (!vits_item_ok(items[i]))
-            return set_error(GSV_E_ARG, "bad vocoder item " + std::to_string(i));
-    if (int r = vits_norm_ok(items, norm, n)) return r;
+    if (int r = vits_entry_ok(eng, items, norm, n, false, 1)) return r;
     if (int r = eng->vits_batch_finish(nullptr)) return r;
     if (int r = eng->vits_wait(nullptr)) return r;
     eng->vb_items.assign(items, items + n);

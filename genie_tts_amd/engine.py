@@ -503,6 +503,43 @@ def check_loudness(loudness=None, peak=None) -> dict:
     return out if loudness is not None else {}
 
 
+VOCODER_OPTIONS = ("speed", "sample_rate", "pcm16", "loudness", "peak")
+
+
+def vocoder_options(speed=None, sample_rate=None, pcm16=False, loudness=None, peak=None) -> dict:
+    """The options of one vocoder call, validated (ValueError, before any GPU work), as the
+    keywords of Engine.vits_decode / the keys of a vocoder item.  Only what differs from the
+    call without options is returned, so nothing given is that call, with no extra keyword.
+    speed: the speech rate (GPT-SoVITS's `speed`), finite and within 0.25 .. 4; the vocoder
+      runs at T' = vits_frames(G, speed) frames and the audio is 640 T' samples, its pitch
+      unchanged.  No key for None or 1.
+    sample_rate / pcm16: the output stage behind the vocoder, on the GPU (Engine.audio_convert):
+      the audio at one of SAMPLE_RATES, audio_samples(640 T', sample_rate) samples, and / or as
+      saturated int16.  Neither: float32 at 32 kHz.
+    loudness / peak: the audio measured by ITU-R BS.1770-4 and brought to `loudness` LUFS
+      (within [-50, -5]; e.g. -16 for speech, EBU R 128's -23) on the GPU, in front of the
+      conversion, the gain limited so that the 32 kHz sample peak stays under `peak` (linear,
+      (0, 1]; None: -1 dBFS).  With loudness alone the audio is float32 at 32 kHz, normalised.
+      A `peak` without a `loudness` is validated and dropped."""
+    out = {}
+    if speed is not None:
+        vits_frames(0, speed)
+        if float(speed) != 1.0:
+            out["speed"] = float(speed)
+    out.update(check_out_format(sample_rate, pcm16))
+    out.update(check_loudness(loudness, peak))
+    return out
+
+
+def vocoder_options_each(n: int, speed=1.0, sample_rate=None, pcm16=False, loudness=None, peak=None) -> List[dict]:
+    """vocoder_options of n items, each option one value for all of them or one per item."""
+    cols = [[v] * n if v is None or np.ndim(v) == 0 else list(v) for v in (speed, sample_rate, pcm16, loudness, peak)]
+    for what, group in (("speed", cols[:1]), ("sample_rate / pcm16", cols[1:3]), ("loudness / peak", cols[3:])):
+        if any(len(c) != n for c in group):
+            raise ValueError(f"{what}: one value, or one per item")
+    return [vocoder_options(*row) for row in zip(*cols)]
+
+
 def loudness_coeffs(rate: int):
     """gsv_loudness_coeffs: the K-weighting biquads at `rate` as float64 [10] (shelf b0 b1 b2 a1
     a2, high-pass b0 b1 b2 a1 a2).  Host only: needs the library, not a GPU."""
@@ -1018,45 +1055,21 @@ class Engine:
                     peak: Optional[float] = None):
         """vits_fp32.onnx for one utterance.  Noise of z_p: eps (tensor/array [192, T']) if
         given, else the engine's Philox N(0,1) stream keyed by noise_seed if given, else zeros.
-        speed: the speech rate (0.25 .. 4; T' = vits_frames(G, speed) frames, 640 T' samples).
-        sample_rate / pcm16: the output stage (see audio_convert) behind the vocoder, on the GPU;
-        the result is then the converted tensor (the 32 kHz float32 one: self.vits_audio_32k[0]).
-        loudness / peak: the result normalised to that target in LUFS under the peak ceiling (see
-        audio_convert), measured and applied on the GPU; its stats: self.vits_loudness[0]."""
-        fmt = check_out_format(sample_rate, pcm16)
-        fmt.update(check_loudness(loudness, peak))
+        speed, sample_rate / pcm16, loudness / peak: see vocoder_options.  With an output format or
+        a loudness target the result is the output stage's tensor; the 32 kHz float32 audio is
+        self.vits_audio_32k[0] and the loudness stats (device float32 [4]) self.vits_loudness[0]."""
+        item = dict(text_seq=text_seq, pred_semantic=pred_semantic, ref_audio=ref_audio, ge=ge,
+                    ge_advanced=ge_advanced, speed=speed, sample_rate=sample_rate, pcm16=pcm16, loudness=loudness,
+                    peak=peak)
         if noise_seed is not None and eps is None:
-            return self.vits_decode_batch([dict(text_seq=text_seq, pred_semantic=pred_semantic, ref_audio=ref_audio,
-                                                ge=ge, ge_advanced=ge_advanced, noise_seed=noise_seed,
-                                                speed=speed, **fmt)], noise_scale)[0]
-        if float(speed) != 1.0 or fmt:
-            norm = []
-            item, keep, audio = self._vits_item(dict(text_seq=text_seq, pred_semantic=pred_semantic,
-                                                     ref_audio=ref_audio, ge=ge, ge_advanced=ge_advanced, eps=eps,
-                                                     speed=speed, **fmt), norm)
-            if norm[0][0].target:
-                _check(lib().gsv_vits_decode_item_norm(self.h, ctypes.byref(item), ctypes.byref(norm[0][0]),
-                                                       ctypes.c_float(noise_scale), _stream()),
-                       "gsv_vits_decode_item_norm")
-            else:
-                _check(lib().gsv_vits_decode_item(self.h, ctypes.byref(item), ctypes.c_float(noise_scale), _stream()),
-                       "gsv_vits_decode_item")
-            self.vits_audio_32k = [keep[-1] if item.out else audio]
-            self.vits_loudness = [norm[0][1]]
-            return audio
-        t = self.torch
-        ts = self._ids(text_seq)
-        sem = self._ids(pred_semantic)
-        G = sem.numel()
-        ra = None if ref_audio is None else self._dev(ref_audio, t.float32).reshape(-1)
-        g = None if ge is None else self._dev(ge, t.float32).reshape(-1)
-        ga = None if ge_advanced is None else self._dev(ge_advanced, t.float32).reshape(-1)
-        e = None if eps is None else self._dev(eps, t.float32).reshape(192, 2 * G)
-        audio = t.empty((1280 * G,), dtype=t.float32, device=self.dev)
-        _check(lib().gsv_vits_decode(self.h, _ptr(ts), ts.numel(), _ptr(sem), G, _ptr(ra),
-                                     0 if ra is None else ra.numel(), _ptr(g), _ptr(ga), _ptr(e),
-                                     ctypes.c_float(noise_scale), _ptr(audio), _stream()),
-               "gsv_vits_decode")
+            return self.vits_decode_batch([dict(item, noise_seed=noise_seed)], noise_scale)[0]
+        norm = []
+        it, keep, audio = self._vits_item(dict(item, eps=eps), norm)
+        ld, stats = norm[0]
+        _check(lib().gsv_vits_decode_item_norm(self.h, ctypes.byref(it), None if stats is None else ctypes.byref(ld),
+                                               ctypes.c_float(noise_scale), _stream()), "gsv_vits_decode_item_norm")
+        self.vits_audio_32k = [keep[-1] if it.out else audio]
+        self.vits_loudness = [stats]
         return audio
 
     def audio_convert(self, audio, sample_rate: int = 32000, pcm16: bool = False, loudness: Optional[float] = None,
@@ -1111,10 +1124,11 @@ class Engine:
     vits_loudness: list = []       # its items' loudness stats (device float32 [4]; None: not normalised)
 
     def _vits_item(self, it: dict, norm: Optional[list] = None):
-        """(VitsItem, tensors it points at, result tensor) of one vocoder call.  With the item
-        keys sample_rate / pcm16 / loudness the result is the output stage's tensor (the item's
-        `out`), and the 32 kHz float32 audio, still written, is the last of the kept tensors.
-        norm: a list that receives the item's (Loudness, stats tensor or None)."""
+        """(VitsItem, tensors it points at, result tensor) of one vocoder call, its option keys
+        resolved by vocoder_options.  With sample_rate / pcm16 / loudness the result is the output
+        stage's tensor (the item's `out`), and the 32 kHz float32 audio, still written, is the last
+        of the kept tensors.  norm: a list that receives the item's (Loudness, stats tensor or None)."""
+        opts = vocoder_options(*(it.get(k) for k in VOCODER_OPTIONS))
         t = self.torch
         ts, sem = self._ids(it["text_seq"]), self._ids(it["pred_semantic"])
         G = sem.numel()
@@ -1124,8 +1138,7 @@ class Engine:
         g = None if g is None else self._dev(g, t.float32).reshape(-1)
         ga = it.get("ge_advanced")
         ga = None if ga is None else self._dev(ga, t.float32).reshape(-1)
-        speed = it.get("speed")
-        speed = 1.0 if speed is None else float(speed)
+        speed = opts.get("speed", 1.0)
         frames = vits_frames(G, speed)
         e = it.get("eps")
         e = None if e is None else self._dev(e, t.float32).reshape(192, frames)
@@ -1136,16 +1149,16 @@ class Engine:
                         0 if ra is None else ra.numel(), 0 if g is None else g.data_ptr(),
                         0 if ga is None else ga.data_ptr(), 0 if e is None else e.data_ptr(),
                         int(seed or 0) & 0xFFFFFFFFFFFFFFFF, mode, audio.data_ptr(), speed)
-        fmt = check_out_format(it.get("sample_rate"), it.get("pcm16"))
-        ld = check_loudness(it.get("loudness"), it.get("peak"))
-        stats = t.empty((4,), dtype=t.float32, device=self.dev) if ld else None
+        target = opts.get("loudness")
+        stats = None if target is None else t.empty((4,), dtype=t.float32, device=self.dev)
         if norm is not None:
-            norm.append((Loudness(ld["loudness"], ld.get("peak", 0.0), stats.data_ptr()) if ld else Loudness(), stats))
-        elif ld:
+            norm.append((Loudness() if target is None else Loudness(target, opts.get("peak", 0.0), stats.data_ptr()),
+                         stats))
+        elif target is not None:
             raise EngineError("loudness on an entry without a loudness spec")
-        if not fmt and not ld:
+        if opts.keys() <= {"speed"}:
             return item, [ts, sem, ra, g, ga, e], audio
-        rate, pcm = fmt.get("sample_rate", 32000), bool(fmt.get("pcm16"))
+        rate, pcm = opts.get("sample_rate", 32000), "pcm16" in opts
         out = t.empty((audio_samples(640 * frames, rate),), dtype=t.int16 if pcm else t.float32, device=self.dev)
         item.out_rate, item.out_format, item.out = rate, int(pcm), out.data_ptr()
         return item, [ts, sem, ra, g, ga, e, audio], out
@@ -1158,22 +1171,18 @@ class Engine:
     def vits_decode_batch(self, items: Sequence[dict], noise_scale: float = 0.5):
         """Several vocoder calls at once (concurrent engine lanes).  Each item: text_seq,
         pred_semantic, and ref_audio (V2) or ge + ge_advanced (V2ProPlus); optional eps or
-        noise_seed, optional speed.  Returns one audio tensor [640 T'] per item (1280 G at speed 1).
-        Optional sample_rate / pcm16 per item: that item's result is the output stage's tensor
-        (one stage launch for the batch); self.vits_audio_32k then holds every item's 32 kHz audio."""
+        noise_seed, and the option keys of vocoder_options.  Returns one audio tensor [640 T'] per
+        item (1280 G at speed 1), the output stage's where the item asks for it (one stage launch
+        for the batch); self.vits_audio_32k then holds every item's 32 kHz audio."""
         arr, norm, keep, outs, a32 = self._vits_items(items)
-        if norm is not None:
-            _check(lib().gsv_vits_decode_batch_norm(self.h, len(items), arr, norm, ctypes.c_float(noise_scale),
-                                                    _stream()), "gsv_vits_decode_batch_norm")
-        else:
-            _check(lib().gsv_vits_decode_batch(self.h, len(items), arr, ctypes.c_float(noise_scale), _stream()),
-                   "gsv_vits_decode_batch")
+        _check(lib().gsv_vits_decode_batch_norm(self.h, len(items), arr, norm, ctypes.c_float(noise_scale),
+                                                _stream()), "gsv_vits_decode_batch_norm")
         self.vits_audio_32k = a32
         return outs
 
     def _vits_items(self, items: Sequence[dict]):
-        """The item array of a batch, its gsv_loudness array (None when no item has a target: the
-        plain entry is then called), the kept tensors, the results and the 32 kHz tensors."""
+        """The item array of a batch, its gsv_loudness array (None when no item has a target),
+        the kept tensors, the results and the 32 kHz tensors."""
         arr = (VitsItem * len(items))()
         keep, outs, a32, norm = [], [], [], []
         for i, it in enumerate(items):
@@ -1192,12 +1201,8 @@ class Engine:
         beside whatever T2S is issued next.  Returns the audio tensors, valid after
         vits_batch_wait()."""
         arr, norm, keep, outs, a32 = self._vits_items(items)
-        if norm is not None:
-            _check(lib().gsv_vits_decode_batch_async_norm(self.h, len(items), arr, norm, ctypes.c_float(noise_scale),
-                                                          _stream()), "gsv_vits_decode_batch_async_norm")
-        else:
-            _check(lib().gsv_vits_decode_batch_async(self.h, len(items), arr, ctypes.c_float(noise_scale),
-                                                     _stream()), "gsv_vits_decode_batch_async")
+        _check(lib().gsv_vits_decode_batch_async_norm(self.h, len(items), arr, norm, ctypes.c_float(noise_scale),
+                                                      _stream()), "gsv_vits_decode_batch_async_norm")
         self.vits_audio_32k = a32
         # items and device buffers live until the wait -- also a previous batch's, which this
         # call only ordered behind the engine stream (its lanes may still read them)
@@ -1223,15 +1228,11 @@ class Engine:
         audio tensor [640 T'], valid after vits_wait().  item as for vits_decode_batch."""
         norm = []
         it, keep, audio = self._vits_item(item, norm)
-        if norm[0][0].target:
-            _check(lib().gsv_vits_decode_async_norm(self.h, ctypes.byref(it), ctypes.byref(norm[0][0]),
-                                                    ctypes.c_float(noise_scale), _stream()),
-                   "gsv_vits_decode_async_norm")
-        else:
-            _check(lib().gsv_vits_decode_async(self.h, ctypes.byref(it), ctypes.c_float(noise_scale), _stream()),
-                   "gsv_vits_decode_async")
-        self._vits_keep = keep + [norm[0][1]]   # device inputs stay alive until the call is finished
-        self.vits_loudness = [norm[0][1]]
+        ld, stats = norm[0]
+        _check(lib().gsv_vits_decode_async_norm(self.h, ctypes.byref(it), None if stats is None else ctypes.byref(ld),
+                                                ctypes.c_float(noise_scale), _stream()), "gsv_vits_decode_async_norm")
+        self._vits_keep = keep + [stats]   # device inputs stay alive until the call is finished
+        self.vits_loudness = [stats]
         self.vits_audio_32k = [keep[-1] if it.out else audio]
         return audio
 

@@ -25,7 +25,7 @@ from typing import Callable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from .engine import EngineStopped, Sampler, check_loudness, check_out_format, request_stop_all, vits_frames
+from .engine import EngineStopped, Sampler, request_stop_all, vocoder_options, vocoder_options_each
 from .sessions import (EncoderSession, FirstStageDecoderSession, StageDecoderSession, VitsSession,
                        PromptEncoderSession)
 
@@ -105,15 +105,9 @@ class GENIE:
             sampler: Optional[Sampler] = None, speed: float = 1.0, sample_rate: Optional[int] = None,
             pcm16: bool = False, loudness: Optional[float] = None,
             peak: Optional[float] = None) -> Optional[np.ndarray]:
-        """speed: the speech rate (0.25 .. 4, GPT-SoVITS's `speed`; 1: the reference's audio).
-        sample_rate (one of engine.SAMPLE_RATES) / pcm16: the audio at that rate and / or as int16,
-        converted on the GPU behind the vocoder (Engine.audio_convert); neither: 32 kHz float32.
-        loudness (LUFS, -50 .. -5) / peak (linear ceiling, default -1 dBFS): the audio normalised
-        to that BS.1770-4 level on the GPU, in front of the conversion; None: as the vocoder gives it."""
-        vits_frames(0, speed)          # ValueError for a bad rate, before any GPU work
-        rate = {} if float(speed) == 1.0 else {"speed": float(speed)}
-        rate.update(check_out_format(sample_rate, pcm16))   # ValueError for an unsupported sample rate
-        rate.update(check_loudness(loudness, peak))         # ... or a bad loudness target / ceiling
+        """speed, sample_rate / pcm16, loudness / peak: engine.vocoder_options (ValueError for a
+        bad value, before any GPU work); none given: the reference's audio."""
+        rate = vocoder_options(speed, sample_rate, pcm16, loudness, peak)
         if isinstance(text, str):
             if g2p is None:
                 raise ValueError("text input needs a g2p(text, language) callable (G2P is outside this engine)")
@@ -154,19 +148,17 @@ class GENIE:
         the rest (gsv_vits_decode_async), and sentence i+1's encoder + prefill run on
         those CUs during sentence i's decode (gsv_t2s_prefetch), so sentence i is
         yielded once sentence i+1's T2S is done.  Same tokens and audio as calling
-        tts per sentence.  speed: the speech rate of every sentence; sample_rate / pcm16: their
-        output format (as for tts; the stage runs on the vocoder's CUs); loudness / peak: every
-        sentence normalised on its own (as for tts), measured on the vocoder's CUs too."""
-        vits_frames(0, speed)          # a bad rate fails here, before anything is started
-        fmt = check_out_format(sample_rate, pcm16)
-        fmt.update(check_loudness(loudness, peak))
+        tts per sentence.  speed, sample_rate / pcm16, loudness / peak: as for tts, of every
+        sentence on its own; the output stage and the measurement run on the vocoder's CUs too."""
+        opts = vocoder_options(speed, sample_rate, pcm16, loudness, peak)   # a bad value fails before anything starts
+        speed = opts.pop("speed", 1.0)
         eng = _engine_of(encoder, first_stage_decoder, stage_decoder, vocoder)
         if eng is None or vocoder_cus <= 0 or len(texts) < 2:
             for t in texts:
                 if self.stop_event.is_set():
                     return
                 yield self.tts(t, prompt_audio, encoder, first_stage_decoder, stage_decoder, vocoder, prompt_encoder,
-                               language, text_bert, g2p, sampler, speed, **fmt)
+                               language, text_bert, g2p, sampler, speed, **opts)
             return
         prev_cus = eng.vocoder_cus     # restored when the stream ends: later single-sentence and
         if prev_cus != vocoder_cus:    # batched calls keep every CU (decode groups, lanes)
@@ -218,7 +210,7 @@ class GENIE:
                     yield done.cpu().numpy()
                 G = sem.size
                 eps = vocoder.eps(G, speed)
-                item = dict(text_seq=text_seq, pred_semantic=sem, speed=speed, **cond, **fmt)
+                item = dict(text_seq=text_seq, pred_semantic=sem, speed=speed, **cond, **opts)
                 if eps is not None:
                     item["eps"] = eps
                 else:
@@ -278,18 +270,14 @@ class GENIE:
         (text_seq, text_bert|None[, force_steps]).  All sequences decode together
         (one multi-sequence persistent launch, ragged: a finished sequence drops out);
         the vocoder runs each utterance's text/flow part on concurrent lanes and the
-        generator once over the whole batch (gsv_vits_decode_batch).  speed: one speech rate
-        for all items, or one per item.  samplers / streams: one sampler (and Philox stream) per
-        item instead of `sampler`, still one launch (Engine.t2s_generate).  sample_rate / pcm16:
-        the output format, one value for all items or one per item (tts_batch_vocoder); loudness /
-        peak: the loudness target and ceiling, likewise."""
+        generator once over the whole batch (gsv_vits_decode_batch).  samplers / streams: one
+        sampler (and Philox stream) per item instead of `sampler`, still one launch
+        (Engine.t2s_generate).  speed, sample_rate / pcm16, loudness / peak: one value for all
+        items or one per item (tts_batch_vocoder)."""
         toks = (self.tts_batch_t2s(items, prompt_audio, model, sampler) if samplers is None and streams is None
                 else self.tts_batch_t2s(items, prompt_audio, model, sampler, samplers=samplers, streams=streams))
-        fmt = {} if sample_rate is None and np.ndim(pcm16) == 0 and not pcm16 else dict(sample_rate=sample_rate,
-                                                                                         pcm16=pcm16)
-        if loudness is not None:
-            fmt.update(loudness=loudness, peak=peak)
-        wavs = self.tts_batch_vocoder(items, toks, prompt_audio, model, speed=speed, **fmt)
+        wavs = self.tts_batch_vocoder(items, toks, prompt_audio, model, speed=speed, sample_rate=sample_rate,
+                                      pcm16=pcm16, loudness=loudness, peak=peak)
         return [w if isinstance(w, np.ndarray) else w.cpu().numpy() for w in wavs]
 
     def tts_batch_t2s(self, items: Sequence[tuple], prompt_audio: ReferenceAudio, model, sampler: Sampler,
@@ -312,27 +300,12 @@ class GENIE:
         """The vocoder half of tts_batch.  overlapped=True (engine-backed vocoder only) starts
         the batch on the vocoder lanes and returns device tensors that are valid after
         model.ENGINE.vits_batch_wait(); the T2S of the next batch runs beside it
-        (gsv_vits_decode_batch_async).  sample_rate (None: 32 kHz float32 as ever) / pcm16: the
-        output format, one value or one per item; a batch may mix rates, and the whole batch is
-        converted by one launch of the engine's output stage.  loudness / peak (None: off): a target
-        in LUFS and a peak ceiling, one value or one per item (None entries: that item as ever); the
-        items with a target are measured in one pass and their gains applied by that same launch."""
+        (gsv_vits_decode_batch_async).  speed, sample_rate / pcm16, loudness / peak
+        (engine.vocoder_options): one value or one per item (None entries: that item as ever).  A
+        batch may mix them: one launch of the engine's output stage converts the whole batch, and
+        the items with a target are measured in one pass and their gains applied by that launch."""
         eng = model.ENGINE
-        speeds = [float(speed)] * len(items) if np.ndim(speed) == 0 else [float(v) for v in speed]
-        if len(speeds) != len(items):
-            raise ValueError("speed: one value, or one per item")
-        for v in speeds:
-            vits_frames(0, v)          # ValueError for a bad rate, before any GPU work
-        rates = [sample_rate] * len(items) if sample_rate is None or np.ndim(sample_rate) == 0 else list(sample_rate)
-        pcms = [bool(pcm16)] * len(items) if np.ndim(pcm16) == 0 else [bool(v) for v in pcm16]
-        if len(rates) != len(items) or len(pcms) != len(items):
-            raise ValueError("sample_rate / pcm16: one value, or one per item")
-        louds = [loudness] * len(items) if loudness is None or np.ndim(loudness) == 0 else list(loudness)
-        peaks = [peak] * len(items) if peak is None or np.ndim(peak) == 0 else list(peak)
-        if len(louds) != len(items) or len(peaks) != len(items):
-            raise ValueError("loudness / peak: one value, or one per item")
-        fmts = [check_out_format(r, p) for r, p in zip(rates, pcms)]   # ValueError for an unsupported rate
-        fmts = [dict(f, **check_loudness(l, k)) for f, l, k in zip(fmts, louds, peaks)]
+        opts = vocoder_options_each(len(items), speed, sample_rate, pcm16, loudness, peak)   # before any GPU work
         if model.PROMPT_ENCODER is not None:
             prompt_audio.update_global_emb(model.PROMPT_ENCODER)
         cond = ({"ref_audio": prompt_audio.audio_32k} if model.PROMPT_ENCODER is None else
@@ -340,12 +313,11 @@ class GENIE:
         if model.PROMPT_ENCODER is None and getattr(model.VITS, "engine", None) is eng:
             cond = model.VITS.v2_cond(prompt_audio.audio_32k)   # the reference branch once per reference
         if getattr(model.VITS, "engine", None) is not eng:
-            return [model.VITS.run(None, {"text_seq": it[0], "pred_semantic": tok.reshape(1, 1, -1), **cond,
-                                          **({} if v == 1.0 else {"speed": v}), **f})[0]
-                    for it, tok, v, f in zip(items, toks, speeds, fmts)]
+            return [model.VITS.run(None, {"text_seq": it[0], "pred_semantic": tok.reshape(1, 1, -1), **cond, **o})[0]
+                    for it, tok, o in zip(items, toks, opts)]
         # engine-backed vocoder: all utterances on concurrent lanes (gsv_vits_decode_batch)
-        batch = [dict(text_seq=it[0], pred_semantic=tok, noise_seed=model.VITS.next_seed(), speed=v, **cond, **f)
-                 for it, tok, v, f in zip(items, toks, speeds, fmts)]
+        batch = [dict(text_seq=it[0], pred_semantic=tok, noise_seed=model.VITS.next_seed(), **cond, **o)
+                 for it, tok, o in zip(items, toks, opts)]
         if overlapped:
             return eng.vits_decode_batch_async(batch, model.VITS.noise_scale)
         return eng.vits_decode_batch(batch, model.VITS.noise_scale)

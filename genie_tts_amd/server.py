@@ -62,8 +62,8 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
     import numpy as np
     import genie_tts_amd as genie
     from genie_tts_amd import api, audio as A
-    from genie_tts_amd.engine import (SAMPLING_FIELDS, audio_samples, check_loudness, check_sampling, make_sampler,
-                                      override_sampler, sampler_key, vits_frames)
+    from genie_tts_amd.engine import (SAMPLING_FIELDS, check_sampling, make_sampler, override_sampler, sampler_key,
+                                      vocoder_options)
     from genie_tts_amd.inference import tts_client
     from genie_tts_amd.model_manager import model_manager
     from genie_tts_amd.text_splitter import TextSplitter
@@ -118,35 +118,21 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
         if not sents:
             reply(kind="end", id=msg["id"])
             return
-        speed = msg.get("speed")
-        try:                          # a bad rate ends this request only (HTTP 400), never a round
-            speed = 1.0 if speed is None else float(speed)
-            vits_frames(0, speed)
-        except (TypeError, ValueError) as e:
-            reply(kind="error", id=msg["id"], detail=f"speed: {e}")
-            return
-        try:                          # likewise a bad sampling control (top_k, top_p, temperature, ...)
-            sampling = check_sampling(**{k: msg.get(k) for k in SAMPLING_FIELDS})
-        except (TypeError, ValueError) as e:
-            reply(kind="error", id=msg["id"], detail=f"sampling: {e}")
-            return
-        out_rate = msg.get("sample_rate")   # None: 32 kHz, converted to PCM on the host as ever
-        try:                          # likewise an output rate the engine's output stage does not have
-            if out_rate is not None:
-                audio_samples(0, out_rate)
-                out_rate = int(out_rate)
-        except (TypeError, ValueError) as e:
-            reply(kind="error", id=msg["id"], detail=f"sample_rate: {e}")
-            return
+        got = {}                      # a bad value ends this request only (HTTP 400), never a round
+        for prefix, check in (("speed", lambda: vocoder_options(speed=msg.get("speed"))),
+                              ("sampling", lambda: check_sampling(**{k: msg.get(k) for k in SAMPLING_FIELDS})),
+                              ("sample_rate", lambda: vocoder_options(sample_rate=msg.get("sample_rate"))),
+                              ("loudness", lambda: vocoder_options(loudness=msg.get("loudness"), peak=msg.get("peak")))):
+            try:
+                got[prefix] = check()
+            except (TypeError, ValueError) as e:
+                reply(kind="error", id=msg["id"], detail=f"{prefix}: {e}")
+                return
+        # sample_rate None: 32 kHz, converted to PCM on the host; no loudness key without a target
         r = {"id": msg["id"], "character_name": msg["character_name"], "sentences": sents, "next": 0,
              "force_steps": int(msg.get("force_steps") or 0), "save_path": msg.get("save_path"),
-             "chunks": [], "speed": speed, "sampling": sampling, "sampler": None, "sample_rate": out_rate}
-        if "loudness" in msg or "peak" in msg:   # a request without them is accepted exactly as before
-            try:                      # likewise a loudness target or peak ceiling out of range
-                r.update(check_loudness(msg["loudness"] if "loudness" in msg else None, msg.get("peak")))
-            except (TypeError, ValueError) as e:
-                reply(kind="error", id=msg["id"], detail=f"loudness: {e}")
-                return
+             "chunks": [], "speed": got["speed"].get("speed", 1.0), "sampling": got["sampling"], "sampler": None,
+             "sample_rate": got["sample_rate"].get("sample_rate"), **got["loudness"]}
         resolve_sampler(r, model_manager.get(r["character_name"]))
         pending.append(r)
 
@@ -542,8 +528,8 @@ def create_app(router: Router):
     @app.post("/tts")
     async def tts_endpoint(payload: TTSPayload):
         try:
-            from .engine import check_loudness
-            check_loudness(payload.loudness, payload.peak)
+            from .engine import vocoder_options
+            vocoder_options(loudness=payload.loudness, peak=payload.peak)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=f"loudness: {e}")
         gen = router.tts(character_name=payload.character_name, text=payload.text,

@@ -24,7 +24,7 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from .engine import Engine, make_sampler
+from .engine import VOCODER_OPTIONS, Engine, make_sampler, vocoder_options
 
 N_LAYERS = 24
 
@@ -174,17 +174,10 @@ class VitsSession(_Session):
     Philox N(0,1) stream, a fresh seed per call; noise="zero" is the deterministic
     test mode; `eps_fn(G) -> [192, 2G]` fixes it explicitly.
 
-    Speech rate: an optional "speed" feed entry (a scalar, 0.25 .. 4, default 1; the graph was
-    exported with it fixed at 1) resamples the latent to T' = engine.vits_frames(G, speed) frames
-    before enc_p.proj, so the audio is 640 T' samples at unchanged pitch.  eps_fn is then called
-    as `eps_fn(G, T') -> [192, T']`.
-
-    Output format: optional "sample_rate" (one of engine.SAMPLE_RATES) and "pcm16" feed entries
-    run the engine's output stage behind the vocoder (Engine.audio_convert): the audio is then
-    engine.audio_samples(640 T', sample_rate) samples, float32 or int16.  Optional "loudness" (a
-    target in LUFS, -50 .. -5) and "peak" (a linear ceiling in (0, 1], default -1 dBFS) entries have
-    the audio measured by ITU-R BS.1770-4 and brought to that level on the GPU, in front of the
-    conversion (Engine.audio_convert); the 32 kHz float32 audio is still written unnormalised."""
+    Optional feed entries "speed", "sample_rate", "pcm16", "loudness" and "peak": the call's
+    engine.vocoder_options (the graph was exported with speed fixed at 1 and has no output stage).
+    At a speed the latent is resampled to T' frames before enc_p.proj, and eps_fn is called as
+    `eps_fn(G, T') -> [192, T']`."""
     OUTPUTS = (NodeArg("audio", ("1280*G",), "tensor(float)"),)
 
     def __init__(self, engine, version: str, noise_scale: float = 0.5, eps_fn=None, noise: str = "philox",
@@ -238,8 +231,10 @@ class VitsSession(_Session):
         f = input_feed
         self._need(f, "text_seq", "pred_semantic")
         sem = np.asarray(f["pred_semantic"]).reshape(-1)
-        speed = f.get("speed")
-        speed = 1.0 if speed is None else float(np.asarray(speed).reshape(-1)[0])
+        speed = f.get("speed")            # a scalar in any shape, as a feed entry is
+        opts = vocoder_options(None if speed is None else np.asarray(speed).reshape(-1)[0],
+                               *(f.get(k) for k in VOCODER_OPTIONS[1:]))
+        speed = opts.pop("speed", 1.0)
         eps = self.eps(sem.size, speed)
         seed = None if eps is not None else self.next_seed()
         if self.version == "v2":
@@ -248,10 +243,8 @@ class VitsSession(_Session):
         else:
             self._need(f, "ge", "ge_advanced")
             cond = dict(ge=f["ge"], ge_advanced=f["ge_advanced"])
-        # none given: today's call
-        fmt = {k: f[k] for k in ("sample_rate", "pcm16", "loudness", "peak") if f.get(k) is not None}
         audio = self.engine.vits_decode(f["text_seq"], sem, eps=eps, noise_scale=self.noise_scale, noise_seed=seed,
-                                        speed=speed, **cond, **fmt)
+                                        speed=speed, **cond, **opts)
         return self._select(output_names, {"audio": _np(audio)})
 
 

@@ -370,7 +370,7 @@ typedef struct { float target; float peak; float* stats; } gsv_loudness;
 /* out = shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2 at `rate`.  Pure: needs no device. */
 int gsv_loudness_coeffs(int32_t rate, double* out /* [10] */);
 /* The `_norm` twins of the entries that take items: norm is [n] (one per item; NULL: the plain
- * call, which these are then bit for bit, launch for launch).  A batch is one measurement pass
+ * call, which forwards here: one set of checks, the same launches).  A batch is one measurement pass
  * plus one stage launch per 256 items; after an fp16-range re-run the re-run's audio is measured;
  * under gsv_vits_decode_async_norm both run on the vocoder's stream.  norm is copied: it need
  * not outlive the call (the stats buffers must, until the wait). */

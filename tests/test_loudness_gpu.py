@@ -353,6 +353,65 @@ def test_fp16_range_rerun_measures_the_reruns_audio(setup):
     _same_as_normalize(e, out, st, a32, None, False, -16.0, None, (ver, "async rerun"))
 
 
+def test_methods_without_a_target_give_the_plain_entries_bits(setup):
+    """The Engine's vocoder methods call the `_norm` entries whether or not an item has a target.
+    Without one, each returns the bits of a direct call of the plain C entry on the same item
+    (G = 8, 3 text ids, Philox noise from one seed), as float32 at 32 kHz and as int16 at 16 kHz.
+    vits_decode takes the batch entry with a seed and the item entry without one (zero noise)."""
+    import torch
+    from genie_tts_amd.engine import _check, _stream, lib
+    ver, e = setup
+    L, f = lib(), ctypes.c_float(0.5)
+    txt, sem = _utt(8, 3)
+    seeded = dict(text_seq=txt, pred_semantic=sem, noise_seed=7, **_cond(ver))
+    unseeded = {k: v for k, v in seeded.items() if k != "noise_seed"}
+
+    def kwargs(it):
+        return {k: v for k, v in it.items() if k not in ("text_seq", "pred_semantic")}
+
+    def wait(out, fn):
+        fn()
+        return out
+    routes = (
+        ("vits_decode, seed", seeded, lambda it: e.vits_decode(txt, sem, **kwargs(it)),
+         lambda item: L.gsv_vits_decode_batch(e.h, 1, ctypes.byref(item), f, _stream())),
+        ("vits_decode, no seed", unseeded, lambda it: e.vits_decode(txt, sem, **kwargs(it)),
+         lambda item: L.gsv_vits_decode_item(e.h, ctypes.byref(item), f, _stream())),
+        ("vits_decode_batch", seeded, lambda it: e.vits_decode_batch([it])[0],
+         lambda item: L.gsv_vits_decode_batch(e.h, 1, ctypes.byref(item), f, _stream())),
+        ("vits_decode_batch_async", seeded, lambda it: wait(e.vits_decode_batch_async([it])[0], e.vits_batch_wait),
+         lambda item: L.gsv_vits_decode_batch_async(e.h, 1, ctypes.byref(item), f, _stream()) or
+         L.gsv_vits_batch_wait(e.h, _stream())),
+        ("vits_decode_async", seeded, lambda it: wait(e.vits_decode_async(it), e.vits_wait),
+         lambda item: L.gsv_vits_decode_async(e.h, ctypes.byref(item), f, _stream()) or
+         L.gsv_vits_wait(e.h, _stream())))
+    for what, base, method, entry in routes:
+        if what == "vits_decode_async":                              # on its own CUs, as above
+            e.set_vocoder_cus(64)
+        try:
+            for opts in ({}, dict(sample_rate=16000, pcm16=True)):
+                it = dict(base, **opts)
+                item, keep, want = e._vits_item(it)
+                _check(entry(item), what)
+                got = method(it)
+                assert e.vits_loudness == [None], what
+                assert got.dtype == want.dtype == (torch.int16 if opts else torch.float32), what
+                assert got.shape == want.shape == ((640 * 8,) if opts else (1280 * 8,)), what
+                assert torch.equal(got, want), (ver, what, opts)
+                assert bool(want.any()), what                       # audio, not an untouched buffer
+        finally:
+            if e.vocoder_cus:
+                e.set_vocoder_cus(0)
+    audio = torch.empty(1280 * 8, device=e.dev)                      # ... and of gsv_vits_decode, the item-less entry
+    c = {k: e._dev(v, torch.float32).reshape(-1) for k, v in _cond(ver).items()}
+    ts, sm = e._ids(txt), e._ids(sem)
+    p = lambda t: ctypes.c_void_p(0 if t is None else t.data_ptr())
+    ra = c.get("ref_audio")
+    _check(L.gsv_vits_decode(e.h, p(ts), 3, p(sm), 8, p(ra), 0 if ra is None else ra.numel(), p(c.get("ge")),
+                             p(c.get("ge_advanced")), None, f, p(audio), _stream()), "gsv_vits_decode")
+    assert torch.equal(e.vits_decode(txt, sem, **_cond(ver)), audio)
+
+
 # ------------------------------------------------------------------ top level
 def test_api_tts_and_stream_normalised(monkeypatch):
     """tts of two sentences with loudness=-16 equals the two single calls; tts_async's chunks at
