@@ -38,8 +38,8 @@ from typing import AsyncIterator, Callable, Dict, List, Optional, Sequence, Unio
 import numpy as np
 
 from . import audio as A
-from .engine import vocoder_options
-from .inference import ReferenceAudio, tts_client
+from .engine import mix_weights, vocoder_options
+from .inference import ReferenceAudio, clear_ge_cache, tts_client
 from .model_manager import model_manager
 from .text_splitter import TextSplitter
 
@@ -122,7 +122,17 @@ def load_weights(character_name: str, weights, version: str, language: str = "Ja
 
 
 def unload_character(character_name: str) -> None:
+    m = model_manager.character_to_model.get(character_name.lower())
+    eng = getattr(m, "ENGINE", None)
     model_manager.remove_character(character_name)
+    if eng is None:
+        return
+    # fused references: this character's per-clip embeddings and mixes live on its engine and go
+    # with it; other characters' stay cached
+    clear_ge_cache(eng)
+    for ref in list(_reference_audios.values()) + list(_clip_cache.values()):
+        if isinstance(ref, ReferenceAudio):
+            ref.drop_engine(eng)
 
 
 def _text_features(text: str, language: str, phonemes_seq=None, text_bert=None):
@@ -142,17 +152,42 @@ def _text_features(text: str, language: str, phonemes_seq=None, text_bert=None):
     return ps, tb
 
 
-def set_reference_audio(character_name: str, audio_path: Union[str, os.PathLike], audio_text: str,
-                        language: Optional[str] = None, *, phonemes_seq=None, text_bert=None,
-                        ssl_content=None, sv_emb=None) -> None:
-    """Internal.py:143-190 + ReferenceAudio.py:28-57: the clip at 32 kHz (+0.3 s
-    silence) and 16 kHz, the prompt text's phones/BERT, the SSL content of the 16 kHz
-    clip; cached per clip path (LRU, Max_Cached_Reference_Audio)."""
-    path = os.fspath(audio_path)
+def _check_ext(path: str) -> bool:
     ext = os.path.splitext(path)[1].lower()
     if ext not in SUPPORTED_AUDIO_EXTS:
         logger.error("Audio format '%s' is not supported. Only the following formats are supported: %s", ext,
                      sorted(SUPPORTED_AUDIO_EXTS))
+        return False
+    return True
+
+
+def _sv_list(aux_sv_emb, n: int) -> list:
+    """aux_sv_emb as one entry per auxiliary clip (None: from the SV model)."""
+    if aux_sv_emb is None:
+        return [None] * n
+    if len(aux_sv_emb) != n:
+        raise ValueError(f"aux_sv_emb: one per auxiliary clip ({n}), None where the SV model supplies it")
+    return [None if e is None else np.asarray(e, np.float32).reshape(1, -1) for e in aux_sv_emb]
+
+
+def set_reference_audio(character_name: str, audio_path: Union[str, os.PathLike], audio_text: str,
+                        language: Optional[str] = None, *, phonemes_seq=None, text_bert=None,
+                        ssl_content=None, sv_emb=None, aux_audio_paths=None, aux_weights=None,
+                        aux_sv_emb=None) -> None:
+    """Internal.py:143-190 + ReferenceAudio.py:28-57: the clip at 32 kHz (+0.3 s
+    silence) and 16 kHz, the prompt text's phones/BERT, the SSL content of the 16 kHz
+    clip; cached per clip path (LRU, Max_Cached_Reference_Audio).
+    aux_audio_paths: auxiliary clips whose timbre is fused with the primary's (GPT-SoVITS's
+    aux_ref_audio_paths; inference.ReferenceAudio), read like the primary -- same formats, same
+    duration warning -- and needing no text.  aux_weights: one weight per clip, primary first
+    (engine.mix_weights; None: the plain mean), checked before any file is read (ValueError).
+    aux_sv_emb (V2ProPlus): one per auxiliary clip, None where the SV model supplies it.  With
+    auxiliary clips the cache key is (path, aux paths, weights)."""
+    path = os.fspath(audio_path)
+    aux_paths = [] if aux_audio_paths is None else [os.fspath(p) for p in aux_audio_paths]
+    weights = mix_weights(1 + len(aux_paths), aux_weights) if aux_paths or aux_weights is not None else None
+    aux_sv = _sv_list(aux_sv_emb, len(aux_paths))
+    if not all([_check_ext(p) for p in [path, *aux_paths]]):
         return
     if language is None:
         m = model_manager.get(character_name)
@@ -162,10 +197,13 @@ def set_reference_audio(character_name: str, audio_path: Union[str, os.PathLike]
     language = _norm_language(language)
     if language not in ("Japanese", "English", "Chinese"):
         raise ValueError("Unknown language")
-    ref = _clip_cache.get(path)
+    key = (path, tuple(aux_paths), weights.tobytes()) if aux_paths else path
+    ref = _clip_cache.get(key)
     if ref is None:
         audio_32k = A.load_audio(path, 32000).reshape(1, -1)
         audio_16k = A.resample(audio_32k[0], 32000, 16000).reshape(1, -1)
+        aux_32k = [A.load_audio(p, 32000).reshape(1, -1) for p in aux_paths]
+        aux_16k = [A.resample(a[0], 32000, 16000).reshape(1, -1) for a in aux_32k]   # V2ProPlus: for the SV model
         if ssl_content is None:
             if _ssl_extractor is not None:
                 ssl_content = _ssl_extractor(audio_16k)
@@ -179,38 +217,51 @@ def set_reference_audio(character_name: str, audio_path: Union[str, os.PathLike]
         ref = ReferenceAudio(phonemes_seq=ps, text_bert=tb, audio_32k=audio_32k,
                              ssl_content=np.asarray(ssl_content, np.float32).reshape(1, 768, -1),
                              sv_emb=None if sv_emb is None else np.asarray(sv_emb, np.float32).reshape(1, -1),
-                             text=audio_text)
+                             text=audio_text, aux_audio_32k=aux_32k, aux_audio_16k=aux_16k, aux_sv_emb=aux_sv,
+                             weights=weights if aux_paths else None)
         ref.audio_16k = audio_16k
         ref.sv_fn = _sv_extractor
-        _clip_cache[path] = ref
+        _clip_cache[key] = ref
         while len(_clip_cache) > int(os.getenv("Max_Cached_Reference_Audio", "10")):
             _clip_cache.popitem(last=False)
     else:
-        _clip_cache.move_to_end(path)
+        _clip_cache.move_to_end(key)
         if ref.text != audio_text or phonemes_seq is not None:      # ReferenceAudio.py:18-21 set_text
             ref.phonemes_seq, ref.text_bert = _text_features(audio_text, language, phonemes_seq, text_bert)
             ref.text = audio_text
         if sv_emb is not None:
             ref.sv_emb = np.asarray(sv_emb, np.float32).reshape(1, -1)
-            ref.global_emb = ref.global_emb_advanced = None
+            ref.reset_cond()
+        if any(e is not None for e in aux_sv):
+            ref.aux_sv_emb = [new if new is not None else old for new, old in
+                              zip(aux_sv, list(ref.aux_sv_emb) + [None] * len(aux_sv))]
+            ref.reset_cond()
     _reference_audios[character_name] = ref
 
 
 def set_reference_features(character_name: str, phonemes_seq: np.ndarray, text_bert: Optional[np.ndarray],
                            audio_32k: np.ndarray, ssl_content: np.ndarray, sv_emb: Optional[np.ndarray] = None,
-                           audio_text: str = "") -> None:
-    """Set the reference from already-extracted features (the fields GENIE.tts reads)."""
+                           audio_text: str = "", aux_audio_32k=None, aux_sv_emb=None, aux_weights=None) -> None:
+    """Set the reference from already-extracted features (the fields GENIE.tts reads).
+    aux_audio_32k: auxiliary clips (32 kHz float32 arrays) whose timbre is fused with the
+    primary's, aux_weights their weights, primary first (engine.mix_weights; None: the plain
+    mean), aux_sv_emb (V2ProPlus) one sv_emb per auxiliary clip, None where the SV model supplies
+    it: inference.ReferenceAudio.  ValueError for bad weights."""
+    aux = [] if aux_audio_32k is None else [np.asarray(a, np.float32).reshape(1, -1) for a in aux_audio_32k]
+    weights = mix_weights(1 + len(aux), aux_weights) if aux or aux_weights is not None else None
     ps = np.asarray(phonemes_seq, np.int64).reshape(1, -1)
     tb = np.zeros((ps.shape[1], 1024), np.float32) if text_bert is None else np.asarray(text_bert, np.float32)
     _reference_audios[character_name] = ReferenceAudio(
         phonemes_seq=ps, text_bert=tb, audio_32k=np.asarray(audio_32k, np.float32).reshape(1, -1),
         ssl_content=np.asarray(ssl_content, np.float32).reshape(1, 768, -1),
-        sv_emb=None if sv_emb is None else np.asarray(sv_emb, np.float32).reshape(1, -1), text=audio_text)
+        sv_emb=None if sv_emb is None else np.asarray(sv_emb, np.float32).reshape(1, -1), text=audio_text,
+        aux_audio_32k=aux, aux_sv_emb=_sv_list(aux_sv_emb, len(aux)), weights=weights if aux else None)
 
 
 def clear_reference_audio_cache() -> None:
     _reference_audios.clear()
     _clip_cache.clear()
+    clear_ge_cache()                 # the per-clip embeddings of fused references
 
 
 def _sentences(text, split_sentence: bool) -> List:
@@ -223,7 +274,10 @@ def _ensure_sv_emb(m, ref) -> None:
     """V2ProPlus: the reference clip's speaker embedding, once per clip
     (ReferenceAudio.update_global_emb, `g/Audio/ReferenceAudio.py:68-76`): a plugged
     extractor, else the engine's SV model (load_sv_model() or $SV_MODEL_PATH)."""
-    if m.PROMPT_ENCODER is None or ref.sv_emb is not None:
+    if m.PROMPT_ENCODER is None:
+        return
+    _ensure_aux_sv_emb(ref)
+    if ref.sv_emb is not None:
         return
     if getattr(ref, "sv_fn", None) is not None:
         ref.sv_emb = np.asarray(ref.sv_fn(ref.audio_16k), np.float32).reshape(1, -1)
@@ -232,6 +286,30 @@ def _ensure_sv_emb(m, ref) -> None:
         model_manager.load_sv_model()
         sv = model_manager.speaker_verification_model.run(None, {"waveform": ref.audio_16k})[0]
         ref.sv_emb = np.asarray(sv, np.float32).reshape(1, -1)
+
+
+def _ensure_aux_sv_emb(ref) -> None:
+    """The auxiliary clips' speaker embeddings, obtained like the primary's, once per clip: a
+    plugged extractor (ReferenceAudio.aux_sv), else the engine's SV model on the clip's 16 kHz
+    copy (made here for a reference set from arrays).  A clip left without one fails in
+    ReferenceAudio.cond, which names it."""
+    aux = getattr(ref, "aux_audio_32k", None) or []
+    if not aux:
+        return
+    ref.aux_sv_emb = (list(ref.aux_sv_emb) + [None] * len(aux))[:len(aux)]
+    ref.aux_audio_16k = (list(ref.aux_audio_16k) + [None] * len(aux))[:len(aux)]
+    have_sv = model_manager.speaker_verification_model is not None or bool(os.getenv("SV_MODEL_PATH"))
+    for i, a in enumerate(aux):
+        if ref.aux_sv_emb[i] is not None or (ref.sv_fn is None and not have_sv):
+            continue
+        if ref.aux_audio_16k[i] is None:
+            ref.aux_audio_16k[i] = A.resample(np.asarray(a, np.float32).reshape(-1), 32000, 16000).reshape(1, -1)
+        if ref.sv_fn is not None:
+            ref.aux_sv(i)
+        else:
+            model_manager.load_sv_model()
+            sv = model_manager.speaker_verification_model.run(None, {"waveform": ref.aux_audio_16k[i]})[0]
+            ref.aux_sv_emb[i] = np.asarray(sv, np.float32).reshape(1, -1)
 
 
 def _sampling(top_k=None, top_p=None, temperature=None, repetition_penalty=None, seed=None) -> dict:

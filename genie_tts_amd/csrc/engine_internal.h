@@ -546,6 +546,7 @@ struct gsv_engine {
     hipError_t host_wait(hipStream_t st);
     int prompt_encode(const float* ref_audio, int n_audio, const float* sv_emb, float* ge,
                       float* ge_adv, hipStream_t st);
+    void ge_project(const float* ge, float* ge_adv, hipStream_t st);   // its last step: ge_adv = ge_to512(ge)
     // ---- output stage (audio_out.hip): sample rate / int16 of a vocoder item's `out`, gsv_audio_convert
     // The item table's regions, one per call site that may run beside the others: a region's
     // event follows the launch that last read it.

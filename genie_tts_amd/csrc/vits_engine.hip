@@ -1656,11 +1656,17 @@ int gsv_engine::prompt_encode(const float* ref_audio, int n_audio, const float* 
     gemm_nt(g, s);
     add_vec(W.pe_ge, W.sv, W.pe_ge, 1024, s);
     prelu_vec(W.pe_ge, penc.prelu, ge, 1024, s);
+    ge_project(ge, ge_adv, s);
+    return hipGetLastError() == hipSuccess ? 0 : set_error(GSV_E_HIP, "prompt encoder launch");
+}
+
+// ge_adv [512] = ge_to512(ge [1024]) (prompt_encoder#280): the prompt encoder's last step, and what
+// gsv_ge_project runs on a fused ge.  One body, so both give the same bits for the same ge.
+void gsv_engine::ge_project(const float* ge, float* ge_adv, hipStream_t s) {
     GemmArgs a{};
     a.M = 1; a.N = 512; a.K = 1024; a.A = ge; a.lda = 1024; a.W = penc.to512_w; a.ldw = 1024;
     a.bias = penc.to512_b; a.C = ge_adv; a.ldc = 512; a.mode = EPI_STORE;
     gemm_nt(a, s);
-    return hipGetLastError() == hipSuccess ? 0 : set_error(GSV_E_HIP, "prompt encoder launch");
 }
 
 extern "C" int gsv_vits_decode(gsv_engine* eng, const int64_t* text_seq, int32_t n_text,
@@ -1801,6 +1807,19 @@ extern "C" int gsv_prompt_encode(gsv_engine* eng, const float* ref_audio, int32_
     if (int r = eng->vits_batch_finish(nullptr)) return r;
     StreamScope sc(eng, stream);
     return eng->prompt_encode(ref_audio, n_audio, sv_emb, ge, ge_adv, sc.st());
+}
+
+extern "C" int gsv_ge_project(gsv_engine* eng, const float* ge, float* ge_adv, void* stream) {
+    if (!eng) return set_error(GSV_E_ARG, "null engine");
+    if (!ge || !ge_adv) return set_error(GSV_E_ARG, "bad args");
+    hipSetDevice(eng->device);
+    if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
+    if (eng->version != GSV_V2PP || !eng->penc.ready)
+        return set_error(GSV_E_STATE, "ge_to512 needs a V2ProPlus engine with prompt encoder weights");
+    StreamScope sc(eng, stream);
+    (void)hipGetLastError();
+    eng->ge_project(ge, ge_adv, sc.st());
+    return hipGetLastError() == hipSuccess ? 0 : set_error(GSV_E_HIP, "ge_to512 launch");
 }
 
 // ---------------------------------------------------------------- debug hooks

@@ -345,6 +345,8 @@ def lib():
         L.gsv_t2s_generate_finish.argtypes = [vp, vp, i32, vp, vp]
         L.gsv_prompt_encode.argtypes = [vp, vp, i32, vp, vp, vp, vp]
         L.gsv_ref_encode.argtypes = [vp, vp, i32, vp, vp]
+        L.gsv_ge_mix.argtypes = [vp, i32, i32, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_float), vp, vp]
+        L.gsv_ge_project.argtypes = [vp, vp, vp, vp]
         L.gsv_debug_copy.argtypes = [vp, ctypes.c_char_p, vp, ctypes.c_int64, vp]
         L.gsv_debug_conv1d.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
@@ -408,7 +410,7 @@ EXPORTED = (
     "gsv_debug_attn", "gsv_debug_attn_out", "gsv_debug_gemv", "gsv_debug_ffn", "gsv_debug_embed",
     "gsv_loudness_coeffs", "gsv_vits_decode_item_norm", "gsv_vits_decode_batch_norm",
     "gsv_vits_decode_batch_async_norm", "gsv_vits_decode_async_norm", "gsv_audio_loudness",
-    "gsv_audio_normalize", "gsv_debug_loudness_hops",
+    "gsv_audio_normalize", "gsv_debug_loudness_hops", "gsv_ge_mix", "gsv_ge_project",
 )
 
 
@@ -538,6 +540,34 @@ def vocoder_options_each(n: int, speed=1.0, sample_rate=None, pcm16=False, loudn
         if any(len(c) != n for c in group):
             raise ValueError(f"{what}: one value, or one per item")
     return [vocoder_options(*row) for row in zip(*cols)]
+
+
+MIX_MAX = 16             # GSV_MIX_MAX: clips of one fused reference
+
+
+def mix_weights(n: int, weights=None) -> np.ndarray:
+    """The float32 [n] weights of a timbre fusion over n reference clips, primary first
+    (gsv_ge_mix multiplies exactly these): None is equal weights, GPT-SoVITS's plain mean; given
+    weights are normalised to sum 1 in float64 and rounded once to float32.  The one place they
+    are checked: ValueError for n outside 1 .. MIX_MAX, a wrong length, a bool, a non-finite or
+    negative entry, or a zero sum.  Needs no GPU."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= MIX_MAX:
+        raise ValueError(f"a fused reference has 1 .. {MIX_MAX} clips, not {n!r}")
+    n = int(n)
+    if weights is None:
+        return np.full(n, 1.0 / n, np.float64).astype(np.float32)
+    if np.ndim(weights) != 1 or len(weights) != n:
+        raise ValueError(f"weights: one per clip, primary first ({n}), not {weights!r}")
+    for i, v in enumerate(weights):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"weights[{i}] must be a number, not {v!r}")
+        if not math.isfinite(float(v)) or float(v) < 0.0:
+            raise ValueError(f"weights[{i}] must be finite and >= 0, not {v!r}")
+    w = np.array([float(v) for v in weights], np.float64)
+    total = float(w.sum())
+    if not total > 0.0:
+        raise ValueError("weights: at least one must be above 0")
+    return (w / total).astype(np.float32)
 
 
 def loudness_coeffs(rate: int):
@@ -1259,6 +1289,40 @@ class Engine:
         _check(lib().gsv_prompt_encode(self.h, _ptr(ra), ra.numel(), _ptr(sv), _ptr(ge), _ptr(ga),
                                        _stream()), "gsv_prompt_encode")
         return ge, ga
+
+    def ge_mix(self, ges, weights, out=None):
+        """Timbre fusion (gsv_ge_mix): device embeddings ges[i] [dim] (ref_encode's, or
+        prompt_encode's ge) and their float32 weights, as mix_weights returns them -> the device
+        tensor sum_i weights[i] * ges[i], one float32 chain per element in clip order with every
+        multiply and add rounded on its own.  One launch.  out: the result tensor, which may be one
+        of ges.  EngineError for what the entry rejects (n outside 1 .. MIX_MAX, a negative or
+        non-finite weight, no weight above 0), before any launch."""
+        t = self.torch
+        xs = [self._dev(g, t.float32).reshape(-1) for g in ges]
+        dim = xs[0].numel() if xs else 0
+        if any(x.numel() != dim for x in xs):
+            raise ValueError("ge_mix: embeddings of different sizes")
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        if w.size != len(xs):
+            raise ValueError("ge_mix: one weight per embedding")
+        if out is None:
+            out = t.empty((dim,), dtype=t.float32, device=self.dev)
+        ptrs = (ctypes.c_void_p * max(len(xs), 1))(*[x.data_ptr() for x in xs])
+        _check(lib().gsv_ge_mix(self.h, len(xs), dim, ptrs, w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                _ptr(out), _stream()), "gsv_ge_mix")
+        return out
+
+    def ge_project(self, ge):
+        """V2ProPlus: ge [1024] -> ge_advanced [512] = ge_to512(ge) on the device (gsv_ge_project, the
+        last step of prompt_encode alone: prompt_encode's ge gives its ge_advanced bit for bit).  The
+        ge_advanced of a fused voice is this projection of the mixed ge."""
+        t = self.torch
+        g = self._dev(ge, t.float32).reshape(-1)
+        if g.numel() != 1024:
+            raise ValueError("ge_project: ge has 1024 values")
+        ga = t.empty((512,), dtype=t.float32, device=self.dev)
+        _check(lib().gsv_ge_project(self.h, _ptr(g), _ptr(ga), _stream()), "gsv_ge_project")
+        return ga
 
     def hubert(self, audio_16k):
         """CN-HuBERT (gsv_hubert): raw 16 kHz audio [N] -> ssl_content [768, T] on the device."""

@@ -20,17 +20,68 @@ with a caller-supplied `g2p(text, language) -> (text_seq [1,S] i64, text_bert
 from __future__ import annotations
 
 import threading
-from dataclasses import dataclass
+import weakref
+from collections import OrderedDict
+from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from .engine import EngineStopped, Sampler, request_stop_all, vocoder_options, vocoder_options_each
+from .engine import (EngineStopped, Sampler, mix_weights, request_stop_all, vocoder_options,
+                     vocoder_options_each)
 from .sessions import (EncoderSession, FirstStageDecoderSession, StageDecoderSession, VitsSession,
                        PromptEncoderSession)
 
 EOS = 1024
 MAX_STEPS = 500          # Inference.py:95
+
+
+# Per-clip global embeddings of fused references: (id(engine), V2ProPlus?, clip fingerprint) ->
+# (weakref to the engine, ge on its device).  Shared by every ReferenceAudio, so the same clips
+# set again with other weights encode nothing; dropped by clear_ge_cache().  api.tts_async and
+# the replica threads may build a conditioning concurrently: every access holds _ge_lock.
+_ge_cache: "OrderedDict[tuple, tuple]" = OrderedDict()
+_ge_lock = threading.Lock()
+GE_CACHE_MAX = 64
+
+
+def clear_ge_cache(engine=None) -> None:
+    """Forget the per-clip embeddings of fused references: all of them
+    (api.clear_reference_audio_cache), or those on `engine` (api.unload_character) together with
+    those of engines that are gone, whose device tensors the entries would otherwise keep."""
+    with _ge_lock:
+        if engine is None:
+            _ge_cache.clear()
+            return
+        for key in [k for k, (ref, _) in _ge_cache.items() if ref() is None or ref() is engine]:
+            del _ge_cache[key]
+
+
+def _fingerprint(a) -> tuple:
+    """A clip's content key, the one VitsSession.v2_cond uses: size, the float64 sum and 64 samples
+    spread over the clip."""
+    a = np.ascontiguousarray(a, np.float32).reshape(-1)
+    return a.size, float(a.sum(dtype=np.float64)), a[:: max(1, a.size // 64)].tobytes()
+
+
+def _clip_ge(eng, audio_32k, sv_emb=None):
+    """ge of one clip on `eng`, encoded once per (engine, clip): ref_encode (V2), or with the clip's
+    sv_emb prompt_encode's ge (V2ProPlus)."""
+    key = (id(eng), sv_emb is not None, _fingerprint(audio_32k), None if sv_emb is None else _fingerprint(sv_emb))
+    with _ge_lock:
+        hit = _ge_cache.get(key)
+        if hit is not None and hit[0]() is eng:
+            _ge_cache.move_to_end(key)
+            return hit[1]
+    a = np.ascontiguousarray(audio_32k, np.float32).reshape(-1)
+    ge = eng.ref_encode(a) if sv_emb is None else eng.prompt_encode(a, np.asarray(sv_emb, np.float32).reshape(-1))[0]
+    with _ge_lock:
+        for k in [k for k, (ref, _) in _ge_cache.items() if ref() is None]:   # engines that are gone
+            del _ge_cache[k]
+        _ge_cache[key] = (weakref.ref(eng), ge)
+        while len(_ge_cache) > GE_CACHE_MAX:
+            _ge_cache.popitem(last=False)
+    return ge
 
 
 @dataclass
@@ -39,7 +90,16 @@ class ReferenceAudio:
     ReferenceAudio, src/genie_tts/Audio/ReferenceAudio.py:28-76).  api.set_reference_audio
     fills them from a clip: audio.py reads and resamples it (a polyphase restatement of
     soxr HQ), CN-HuBERT (gsv_hubert) gives ssl_content and, for V2ProPlus, the SV model
-    (gsv_sv) gives sv_emb -- both on the engine; or the caller supplies them."""
+    (gsv_sv) gives sv_emb -- both on the engine; or the caller supplies them.
+
+    Timbre fusion (GPT-SoVITS's aux_ref_audio_paths): aux_audio_32k holds further clips of the
+    voice.  Each clip's global embedding is computed on its own by the same reference encoder
+    and the vocoder is conditioned on ge = sum_i w_i ge_i, the primary clip first; `weights` is
+    one weight per clip (engine.mix_weights: normalised to sum 1), None GPT-SoVITS's plain mean.
+    On V2ProPlus every clip needs its own sv_emb (aux_sv_emb, or aux_audio_16k and an SV model),
+    and ge_advanced is ge_to512 of the mixed ge.  The prompt of T2S -- phonemes_seq, text_bert,
+    ssl_content -- is the primary clip's alone: auxiliary clips need no text and run neither G2P
+    nor CN-HuBERT.  cond() is the one place the vocoder's conditioning is built."""
     phonemes_seq: np.ndarray             # i64 [1, R]
     text_bert: np.ndarray                # f32 [R, 1024]
     audio_32k: np.ndarray                # f32 [1, N32]
@@ -50,6 +110,12 @@ class ReferenceAudio:
     text: str = ""
     audio_16k: Optional[np.ndarray] = None               # f32 [1, N16] (set_reference_audio)
     sv_fn: Optional[Callable] = None                     # speaker-verification model, audio_16k -> sv_emb
+    aux_audio_32k: list = field(default_factory=list)    # auxiliary clips, f32 [1, N32] each
+    aux_audio_16k: list = field(default_factory=list)    # their 16 kHz copies (V2ProPlus: for the SV model)
+    aux_sv_emb: list = field(default_factory=list)       # their sv_emb f32 [1, 20480] (None: from the SV model)
+    weights: Optional[np.ndarray] = None                 # one per clip, primary first (None: equal)
+    # the fused conditioning: (id(engine), V2ProPlus?, float32 weights) -> (weakref to the engine, dict)
+    _mix: dict = field(default_factory=dict, repr=False, compare=False)
 
     def update_global_emb(self, prompt_encoder) -> None:
         """ReferenceAudio.py:68-76 (cached after the first call)."""
@@ -62,6 +128,85 @@ class ReferenceAudio:
                              "load_sv_model(), set_sv_extractor() or pass sv_emb")
         self.global_emb, self.global_emb_advanced = prompt_encoder.run(None, {
             "ref_audio": self.audio_32k, "sv_emb": self.sv_emb})
+
+    def aux_sv(self, i: int) -> np.ndarray:
+        """sv_emb of auxiliary clip i (V2ProPlus), obtained like the primary's: given, else sv_fn
+        on its 16 kHz copy (kept).  ValueError naming the clip when there is neither."""
+        while len(self.aux_sv_emb) < len(self.aux_audio_32k):
+            self.aux_sv_emb.append(None)
+        if self.aux_sv_emb[i] is None and self.sv_fn is not None and i < len(self.aux_audio_16k) \
+                and self.aux_audio_16k[i] is not None:
+            self.aux_sv_emb[i] = np.asarray(self.sv_fn(self.aux_audio_16k[i]), np.float32).reshape(1, -1)
+        if self.aux_sv_emb[i] is None:
+            raise ValueError("V2ProPlus needs the speaker-verification embedding (sv_emb) of the reference: "
+                             f"load_sv_model(), set_sv_extractor() or pass sv_emb (auxiliary clip {i})")
+        return self.aux_sv_emb[i]
+
+    def drop_engine(self, engine) -> None:
+        """Forget the fused conditioning cached for `engine` (api.unload_character)."""
+        with _ge_lock:
+            for key in [k for k in self._mix if k[0] == id(engine)]:
+                del self._mix[key]
+
+    def reset_cond(self) -> None:
+        """Forget the cached conditioning (an sv_emb was replaced)."""
+        self.global_emb = self.global_emb_advanced = None
+        with _ge_lock:
+            self._mix.clear()
+
+    def cond(self, vocoder, prompt_encoder=None, engine=None) -> dict:
+        """The conditioning keys of a vocoder call against this reference, the one place they
+        are built (GENIE.tts, tts_stream and tts_batch_vocoder call it).
+        Without auxiliary clips, today's: V2 `ref_audio` for a vocoder that is not engine-backed
+        (or, when the caller names its `engine`, not backed by that one), else the session's
+        v2_cond (gsv_ref_encode once per reference, then its ge); V2ProPlus update_global_emb's
+        ge / ge_advanced.  No mix runs.
+        With auxiliary clips: every clip's ge once per (engine, clip) (_clip_ge), their mix
+        (Engine.ge_mix) and, on V2ProPlus, its projection (Engine.ge_project) once per (engine,
+        weights), as device tensors; later calls are a dictionary look-up.  ValueError for a
+        vocoder that is not engine-backed, bad weights, or a V2ProPlus clip without sv_emb."""
+        eng = getattr(vocoder, "engine", None)
+        backed = eng is not None and hasattr(vocoder, "v2_cond")
+        if not getattr(self, "aux_audio_32k", None):
+            if prompt_encoder is None:
+                own = backed and (engine is None or eng is engine)
+                return vocoder.v2_cond(self.audio_32k) if own else {"ref_audio": self.audio_32k}
+            self.update_global_emb(prompt_encoder)
+            return {"ge": self.global_emb, "ge_advanced": self.global_emb_advanced}
+        if not backed:
+            raise ValueError("timbre fusion (auxiliary reference clips) needs the engine: the vocoder session "
+                             "is not engine-backed")
+        w = mix_weights(1 + len(self.aux_audio_32k), self.weights)
+        v2pp = prompt_encoder is not None
+        key = (id(eng), v2pp, w.tobytes())
+        with _ge_lock:
+            hit = self._mix.get(key)
+        if hit is not None and hit[0]() is eng:
+            return dict(hit[1])
+        if v2pp:
+            if self.sv_emb is None and self.sv_fn is not None and self.audio_16k is not None:
+                self.sv_emb = np.asarray(self.sv_fn(self.audio_16k), np.float32).reshape(1, -1)
+            if self.sv_emb is None:
+                raise ValueError("V2ProPlus needs the speaker-verification embedding (sv_emb) of the reference: "
+                                 "load_sv_model(), set_sv_extractor() or pass sv_emb")
+            svs = [self.sv_emb] + [self.aux_sv(i) for i in range(len(self.aux_audio_32k))]
+        else:
+            svs = [None] * (1 + len(self.aux_audio_32k))
+        ges = [_clip_ge(eng, a, sv) for a, sv in zip([self.audio_32k, *self.aux_audio_32k], svs)]
+        out = {"ge": eng.ge_mix(ges, w)}
+        if v2pp:
+            out["ge_advanced"] = eng.ge_project(out["ge"])
+        with _ge_lock:
+            self._mix[key] = (weakref.ref(eng), out)
+        return dict(out)
+
+
+def _cond(ref, vocoder, prompt_encoder, engine=None) -> dict:
+    """ref.cond(vocoder, prompt_encoder, engine).  A stand-in that only carries the fields GENIE.tts
+    reads (no auxiliary clips) is served by ReferenceAudio.cond all the same."""
+    fn = getattr(ref, "cond", None)
+    return (fn(vocoder, prompt_encoder, engine) if fn is not None
+            else ReferenceAudio.cond(ref, vocoder, prompt_encoder, engine))
 
 
 def eos_filter(semantic_tokens: np.ndarray) -> np.ndarray:
@@ -128,12 +273,8 @@ class GENIE:
             if sem is None:
                 return None
             sem = eos_filter(sem)
-        if prompt_encoder is None:
-            return vocoder.run(None, {"text_seq": text_seq, "pred_semantic": sem,
-                                      "ref_audio": prompt_audio.audio_32k, **rate})[0]
-        prompt_audio.update_global_emb(prompt_encoder)
-        return vocoder.run(None, {"text_seq": text_seq, "pred_semantic": sem, "ge": prompt_audio.global_emb,
-                                  "ge_advanced": prompt_audio.global_emb_advanced, **rate})[0]
+        return vocoder.run(None, {"text_seq": text_seq, "pred_semantic": sem,
+                                  **_cond(prompt_audio, vocoder, prompt_encoder), **rate})[0]
 
     def tts_stream(self, texts: Sequence[Union[str, np.ndarray]], prompt_audio: ReferenceAudio, encoder,
                    first_stage_decoder, stage_decoder, vocoder, prompt_encoder=None, language: str = "japanese",
@@ -164,12 +305,7 @@ class GENIE:
         if prev_cus != vocoder_cus:    # batched calls keep every CU (decode groups, lanes)
             eng.set_vocoder_cus(vocoder_cus)
         try:
-            if prompt_encoder is None:
-                cond = (vocoder.v2_cond(prompt_audio.audio_32k) if getattr(vocoder, "engine", None) is eng
-                        else {"ref_audio": prompt_audio.audio_32k})
-            else:
-                prompt_audio.update_global_emb(prompt_encoder)
-                cond = {"ge": prompt_audio.global_emb, "ge_advanced": prompt_audio.global_emb_advanced}
+            cond = _cond(prompt_audio, vocoder, prompt_encoder, eng)
         except BaseException:          # e.g. a V2ProPlus clip without sv_emb: the CU split is undone
             if eng.vocoder_cus != prev_cus:
                 eng.set_vocoder_cus(prev_cus)
@@ -306,12 +442,7 @@ class GENIE:
         the items with a target are measured in one pass and their gains applied by that launch."""
         eng = model.ENGINE
         opts = vocoder_options_each(len(items), speed, sample_rate, pcm16, loudness, peak)   # before any GPU work
-        if model.PROMPT_ENCODER is not None:
-            prompt_audio.update_global_emb(model.PROMPT_ENCODER)
-        cond = ({"ref_audio": prompt_audio.audio_32k} if model.PROMPT_ENCODER is None else
-                {"ge": prompt_audio.global_emb, "ge_advanced": prompt_audio.global_emb_advanced})
-        if model.PROMPT_ENCODER is None and getattr(model.VITS, "engine", None) is eng:
-            cond = model.VITS.v2_cond(prompt_audio.audio_32k)   # the reference branch once per reference
+        cond = _cond(prompt_audio, model.VITS, model.PROMPT_ENCODER, eng)   # the reference branch once per reference
         if getattr(model.VITS, "engine", None) is not eng:
             return [model.VITS.run(None, {"text_seq": it[0], "pred_semantic": tok.reshape(1, 1, -1), **cond, **o})[0]
                     for it, tok, o in zip(items, toks, opts)]

@@ -97,7 +97,8 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
                 genie.unload_character(msg["character_name"])
             elif cmd == "set_reference_audio":
                 genie.set_reference_audio(msg["character_name"], msg["audio_path"], msg["audio_text"],
-                                          msg["language"])
+                                          msg["language"], aux_audio_paths=msg.get("aux_audio_paths") or None,
+                                          aux_weights=msg.get("aux_weights"))
                 if msg["character_name"] not in api._reference_audios:
                     raise ValueError("reference audio rejected (see worker log)")
             elif cmd == "clear_reference_audio_cache":
@@ -473,6 +474,10 @@ def create_app(router: Router):
         audio_path: str
         audio_text: str
         language: str
+        # timbre fusion (GPT-SoVITS's aux_ref_audio_paths): further clips of the voice, and one
+        # weight per clip, primary first (absent: the plain mean); a bad value is a 400
+        aux_audio_paths: List[str] = []
+        aux_weights: Optional[List[float]] = None
 
     class TTSPayload(BaseModel):
         character_name: str
@@ -516,13 +521,21 @@ def create_app(router: Router):
 
     @app.post("/set_reference_audio")
     async def set_reference_audio_endpoint(payload: ReferenceAudioPayload):
-        ext = os.path.splitext(payload.audio_path)[1].lower()
-        if ext not in SUPPORTED_AUDIO_EXTS:
-            raise HTTPException(status_code=400, detail=f"Audio format '{ext}' is not supported. "
-                                                        f"Supported formats: {sorted(SUPPORTED_AUDIO_EXTS)}")
+        for path in [payload.audio_path, *payload.aux_audio_paths]:
+            ext = os.path.splitext(path)[1].lower()
+            if ext not in SUPPORTED_AUDIO_EXTS:
+                raise HTTPException(status_code=400, detail=f"Audio format '{ext}' is not supported. "
+                                                            f"Supported formats: {sorted(SUPPORTED_AUDIO_EXTS)}")
+        if payload.aux_audio_paths or payload.aux_weights is not None:
+            try:
+                from .engine import mix_weights
+                mix_weights(1 + len(payload.aux_audio_paths), payload.aux_weights)
+            except ValueError as e:
+                raise HTTPException(status_code=400, detail=f"aux_weights: {e}")
         check(await router.broadcast("set_reference_audio", character_name=payload.character_name,
                                      audio_path=payload.audio_path, audio_text=payload.audio_text,
-                                     language=_norm_language(payload.language)))
+                                     language=_norm_language(payload.language),
+                                     aux_audio_paths=list(payload.aux_audio_paths), aux_weights=payload.aux_weights))
         return {"status": "success", "message": f"Reference audio for '{payload.character_name}' set."}
 
     @app.post("/tts")

@@ -177,7 +177,8 @@ class VitsSession(_Session):
     Optional feed entries "speed", "sample_rate", "pcm16", "loudness" and "peak": the call's
     engine.vocoder_options (the graph was exported with speed fixed at 1 and has no output stage).
     At a speed the latent is resampled to T' frames before enc_p.proj, and eps_fn is called as
-    `eps_fn(G, T') -> [192, T']`."""
+    `eps_fn(G, T') -> [192, T']`.  A V2 feed may carry "ge" [512] in place of "ref_audio": the
+    reference's embedding from v2_cond, or a fused one (inference.ReferenceAudio.cond)."""
     OUTPUTS = (NodeArg("audio", ("1280*G",), "tensor(float)"),)
 
     def __init__(self, engine, version: str, noise_scale: float = 0.5, eps_fn=None, noise: str = "philox",
@@ -237,7 +238,9 @@ class VitsSession(_Session):
         speed = opts.pop("speed", 1.0)
         eps = self.eps(sem.size, speed)
         seed = None if eps is not None else self.next_seed()
-        if self.version == "v2":
+        if self.version == "v2" and f.get("ref_audio") is None and f.get("ge") is not None:
+            cond = dict(ge=f["ge"])      # the reference's ge from v2_cond, or a fused one (ReferenceAudio.cond)
+        elif self.version == "v2":
             self._need(f, "ref_audio")
             cond = self.v2_cond(f["ref_audio"])
         else:

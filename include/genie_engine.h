@@ -18,6 +18,8 @@
  *   vocoder.run            (Inference.py:47-60)      gsv_vits_decode
  *   prompt_encoder.run     (ReferenceAudio.py:73)    gsv_prompt_encode
  *   vocoder.run's refer branch (Inference.py:50, V2)  gsv_ref_encode (once per reference)
+ *   aux_ref_audio_paths    (GPT-SoVITS: the mean of the clips' ge in SynthesizerTrn.decode)
+ *                                                    gsv_ge_mix (+ gsv_ge_project on V2ProPlus)
  *   cn_hubert.run          (ReferenceAudio.py:50-52) gsv_hubert
  *   roberta_model.run      (GetPhonesAndBert.py:73)  gsv_roberta (gsv_roberta_batch: many sentences)
  *   per-sentence tts loop  (TTSPlayer.py:56-107)     gsv_t2s_prefetch, gsv_t2s_generate_start /
@@ -442,6 +444,31 @@ int gsv_ref_encode(gsv_engine* eng, const float* ref_audio, int32_t n_audio, flo
  * sv_emb (device [20480]) -> ge (device [1024]), ge_adv (device [512]). */
 int gsv_prompt_encode(gsv_engine* eng, const float* ref_audio, int32_t n_audio,
                       const float* sv_emb, float* ge, float* ge_adv, void* stream);
+
+/* Timbre fusion: GPT-SoVITS's auxiliary reference clips (aux_ref_audio_paths; SynthesizerTrn.decode
+ * with a list of references runs each clip through the reference encoder and averages the global
+ * embeddings).  Each clip is encoded on its own, by gsv_ref_encode (V2, ge [512]) or by
+ * gsv_prompt_encode with the clip's own sv_emb (V2ProPlus, ge [1024]), and the embeddings are
+ * mixed here, once per reference set; the result is the ge of every vocoder entry.
+ *   out[d] = sum_i weights[i] * ge[i][d], as one float32 chain per element in clip order:
+ *     acc = weights[0] * ge[0][d];  acc = acc + weights[i] * ge[i][d]  (i = 1 .. n-1),
+ *   every multiply and add rounded on its own (no fused multiply-add), so a restatement with
+ *   float32 operations gives the same bits, and weights (1, 0, ..) give ge[0] value for value.
+ * ge: HOST array of n device pointers (each [dim]), weights: HOST [n]; both are copied into the
+ * launch's arguments and need not outlive the call.  The caller normalises the weights (the
+ * Python layer: to sum 1 in float64, rounded once to float32; equal weights are GPT-SoVITS's
+ * mean).  n in 1..GSV_MIX_MAX, dim in 1..4096, weights finite and >= 0 with at least one > 0,
+ * else GSV_E_ARG (the message names the index) and nothing is launched.  out (device [dim]) may
+ * be one of the inputs.  Stream-ordered, one launch, no workspace.  Either model version. */
+#define GSV_MIX_MAX 16
+int gsv_ge_mix(gsv_engine* eng, int32_t n, int32_t dim, const float* const* ge, const float* weights,
+               float* out, void* stream);
+/* V2ProPlus: ge_adv (device [512]) = ge_to512(ge (device [1024])), the last GEMV of
+ * gsv_prompt_encode alone (the same call, so given gsv_prompt_encode's ge it returns
+ * gsv_prompt_encode's ge_adv bit for bit).  The ge_adv of a fused voice is this projection of the
+ * mixed ge, as in GPT-SoVITS, not a mix of the clips' ge_adv.  GSV_E_STATE on V2 or without
+ * prompt-encoder weights. */
+int gsv_ge_project(gsv_engine* eng, const float* ge, float* ge_adv, void* stream);
 
 /* chinese-hubert-base.onnx (CN-HuBERT, ReferenceAudio.py:48-52; session loaded at
  * ModelManager.py:172-195): input_values = raw 16 kHz audio (device [n_samples])
