@@ -1256,7 +1256,9 @@ int gsv_engine::persist_enqueue(int B, const gsv_sampler* sp, hipStream_t st, in
     const int pm_groups = std::min({persistm_max_groups(), decode_cus() / persistm_grid(1), B});
     const bool pm = B > 1 && use_persistm && B >= persistm_min_b && pm_groups >= persistm_groups(B);
     if (pm) a.groups = pm_groups;
-    const hipError_t le = B == 1 ? (per ? decode_persist1_each : decode_persist1)(a, st, k0, k1)
+    // B = 1 under option "ptrace": the kernel built with the phase stamps (the product one has none)
+    const hipError_t le = B == 1 && a.trace ? (per ? decode_persist1_trace_each : decode_persist1_trace)(a, st, k0, k1)
+                          : B == 1 ? (per ? decode_persist1_each : decode_persist1)(a, st, k0, k1)
                           : pm   ? (per ? decode_persistm_each : decode_persistm)(a, st, k0, k1)
                                  : (per ? decode_persist1m_each : decode_persist1m)(a, st, k0, k1);
     if (le != hipSuccess)

@@ -347,5 +347,10 @@ hipError_t decode_persistm(const PersistArgs& a, hipStream_t s, hipEvent_t start
 hipError_t decode_persist1_each(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop);
 hipError_t decode_persist1m_each(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop);
 hipError_t decode_persistm_each(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop);
+// The single-sequence kernel built with its phase stamps (a.trace non-null, engine option "ptrace";
+// decode_persist1 / decode_persist1_each take a.trace null only: the product kernels hold no stamp
+// code).  Translation units of their own (t2s_persist1_trace*.hip).
+hipError_t decode_persist1_trace(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop);
+hipError_t decode_persist1_trace_each(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop);
 
 }  // namespace gsv

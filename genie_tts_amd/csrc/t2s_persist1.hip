@@ -69,6 +69,21 @@ constexpr bool SEQ_TABLE = true;
 #define PERSIST_NAME(x) x
 constexpr bool SEQ_TABLE = false;
 #endif
+// PERSIST_TRACE (t2s_persist1_trace.hip, t2s_persist1_trace_each.hip): the single-sequence kernel
+// with its phase stamps compiled in, under the names *_trace / *_trace_each -- translation units
+// of their own for the same reason; the product kernel has no stamp code and no trace branch.
+#if defined(PERSIST_TRACE) && defined(PERSIST_SEQ_TABLE)
+#define PERSIST1_NAME(x) x##_trace_each
+#elif defined(PERSIST_TRACE)
+#define PERSIST1_NAME(x) x##_trace
+#else
+#define PERSIST1_NAME(x) PERSIST_NAME(x)
+#endif
+#ifdef PERSIST_TRACE
+constexpr bool TRACE_UNIT = true;
+#else
+constexpr bool TRACE_UNIT = false;
+#endif
 
 namespace {
 using namespace pk;
@@ -243,6 +258,7 @@ __device__ __forceinline__ unsigned long long* topp_space(Shared1& sh) {
     return reinterpret_cast<unsigned long long*>(sh.at.p);
 }
 
+// (probe is false at compile time in the product kernel, TRACE = false: no stamp code)
 #define STAMP1(i)                                                                         \
     do {                                                                                  \
         if (probe && threadIdx.x == 0) {                                                  \
@@ -834,6 +850,7 @@ __device__ __forceinline__ void pub64(const W& ws, Shared1& sh, int row, unsigne
 // --------------------------------------------------------------------------
 // Attention workgroup: head h of layers grp, grp + G, grp + 2G, ...
 // --------------------------------------------------------------------------
+template <bool TRACE>
 __device__ void run_attn(const PersistArgs& a, const Ws1& ws, Shared1& sh, int grp, int h) {
     const int tid = threadIdx.x, lane = tid & 63, ng = a.groups;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -887,7 +904,7 @@ __device__ void run_attn(const PersistArgs& a, const Ws1& ws, Shared1& sh, int g
         const unsigned tag = ws.tag(s);
         const int kv = kv0 + s;
         for (int l = grp; l < 24; l += ng) {
-            const bool probe = a.trace && ((s == 8 && (l == 12 || l == 13 || l == 23)) || (s == 9 && l == 0));
+            const bool probe = TRACE && a.trace && ((s == 8 && (l == 12 || l == 13 || l == 23)) || (s == 9 && l == 0));
             STAMP1(0);
             if (!form_u(a, ws, s, l, ny0 + s, &sh.p2[0][0], sh, sh.tok)) return;
             STAMP1(1);
@@ -977,7 +994,7 @@ __device__ void run_attn(const PersistArgs& a, const Ws1& ws, Shared1& sh, int g
         }
         // ---- sampler: logits granules of this step -> token -> TK(s + 1)
         if (sampler) {
-            const bool probe = a.trace && s == 8;   // step-end trace (tools/knob_sweep.py)
+            const bool probe = TRACE && a.trace && s == 8;   // step-end trace (tools/knob_sweep.py)
             bool ok = true;
             if (tid == 0) wait_tag16_slow(ws.at(ws.PFH(s, 23, 0)), tag, a.err, ok, a.spin_ticks);
             if (tid == 64) sh.stopreq = ld_stop(a.stop_req);
@@ -1074,6 +1091,7 @@ __device__ void run_attn(const PersistArgs& a, const Ws1& ws, Shared1& sh, int g
 // FFN workgroup: hidden slice j of layers grp, grp + 8, grp + 16 (+ logits rows
 // [64 j, 64 j + 64) in group LOGIT_GRP).
 // --------------------------------------------------------------------------
+template <bool TRACE>
 __device__ void run_ffn(const PersistArgs& a, const Ws1& ws, Shared1& sh, int grp, int j) {
     const int tid = threadIdx.x, lane = tid & 63, ng = a.groups;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1134,7 +1152,7 @@ __device__ void run_ffn(const PersistArgs& a, const Ws1& ws, Shared1& sh, int gr
             break;
         const unsigned tag = ws.tag(s);
         for (int l = grp; l < 24; l += ng) {
-            const bool probe = a.trace && ((s == 8 && (l == 12 || l == 13 || l == 23)) || (s == 9 && l == 0));
+            const bool probe = TRACE && a.trace && ((s == 8 && (l == 12 || l == 13 || l == 23)) || (s == 9 && l == 0));
             STAMP1(0);
             float xv;
             if (!form_x(a, ws, s, l, ny0 + s, &sh.p2[0][0], xv, sh, sh.tok)) return;
@@ -1248,7 +1266,7 @@ __device__ void run_ffn(const PersistArgs& a, const Ws1& ws, Shared1& sh, int gr
             if (probe && tid < 16) a.trace[blockIdx.x * 16 + tid] = sh.stamp[tid];
         }
         if (logits) {
-            const bool probe = a.trace && s == 8;   // step-end trace (tools/knob_sweep.py)
+            const bool probe = TRACE && a.trace && s == 8;   // step-end trace (tools/knob_sweep.py)
             const int lane = opaque_tid() & 63;   // (the row / LDS offsets below: no spilled copies)
             STAMP1(0);
             // ---- logits rows (ar_predict_layer, no bias) of x_24 = LN2_23(h1_23 + b2 + sum PF_23)
@@ -2038,12 +2056,14 @@ __global__ __launch_bounds__(PT) void PERSIST_NAME(k_decode_persist1m)(PersistAr
 
 #else   // the single-sequence kernel
 
-__global__ __launch_bounds__(PT) void PERSIST_NAME(k_decode_persist1)(PersistArgs a) {
+// The product kernel (TRACE_UNIT false) carries no phase stamps; option "ptrace" launches
+// k_decode_persist1_trace, the same code with STAMP1 live (tools/ptrace2.py, tools/knob_sweep.py).
+__global__ __launch_bounds__(PT) void PERSIST1_NAME(k_decode_persist1)(PersistArgs a) {
     __shared__ Shared1 sh;
     const Ws1 ws{a.ring, a.epoch, __builtin_amdgcn_make_buffer_rsrc(a.ring, 0, 0x7fffffff, 0x00020000)};
     const int grp = blockIdx.x / GW, r = blockIdx.x - grp * GW;
-    if (r < 16) run_attn(a, ws, sh, grp, r);
-    else run_ffn(a, ws, sh, grp, r - 16);
+    if (r < 16) run_attn<TRACE_UNIT>(a, ws, sh, grp, r);
+    else run_ffn<TRACE_UNIT>(a, ws, sh, grp, r - 16);
 }
 #endif
 
@@ -2064,16 +2084,17 @@ hipError_t PERSIST_NAME(decode_persist1m)(const PersistArgs& a, hipStream_t s, h
 }
 
 #else
-#ifndef PERSIST_SEQ_TABLE
+#if !defined(PERSIST_SEQ_TABLE) && !defined(PERSIST_TRACE)
 int persist1_grid(int groups) { return groups * GW; }
 int persist1_max_groups() { return NG_MAX; }
 
 size_t persist1_ring_bytes() { return (size_t)Ws1::SLOT * RING1 * 8; }
 #endif
-hipError_t PERSIST_NAME(decode_persist1)(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+hipError_t PERSIST1_NAME(decode_persist1)(const PersistArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
     if (a.groups < 3 || a.groups > NG_MAX) return hipErrorInvalidValue;   // groups 1, 2 own the logits, sampler
     if (SEQ_TABLE != (a.per != nullptr)) return hipErrorInvalidValue;
-    hipExtLaunchKernelGGL(PERSIST_NAME(k_decode_persist1), dim3(a.groups * GW), dim3(PT), 0, s, start, stop, 0, a);
+    if (TRACE_UNIT != (a.trace != nullptr)) return hipErrorInvalidValue;
+    hipExtLaunchKernelGGL(PERSIST1_NAME(k_decode_persist1), dim3(a.groups * GW), dim3(PT), 0, s, start, stop, 0, a);
     return hipGetLastError();
 }
 
