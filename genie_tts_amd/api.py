@@ -401,16 +401,20 @@ def tts(character_name: str, text: Union[str, Sequence[int], np.ndarray], play: 
         top_k: Optional[int] = None, top_p: Optional[float] = None, temperature: Optional[float] = None,
         repetition_penalty: Optional[float] = None, seed: Optional[int] = None,
         sample_rate: Optional[int] = None, loudness: Optional[float] = None,
-        peak: Optional[float] = None) -> Optional[np.ndarray]:
+        peak: Optional[float] = None, pause: Optional[float] = None,
+        trim: Optional[float] = None) -> Optional[np.ndarray]:
     """Internal.py:265-310 (TTSPlayer session: split, synthesize each sentence, save the
     concatenation as 16-bit WAV).  Returns the audio f32 [sum 1280*G_i] at 32 kHz.
     speed, sample_rate, loudness / peak: engine.vocoder_options, per sentence (ValueError for a
     bad value, before anything is synthesized).  The audio is returned, saved (the WAV header
     carries the rate) and played at sample_rate, as float32.
+    pause, trim: the sentence join, per sentence on the GPU (engine.vocoder_options): each sentence
+    is cut to its speech above `trim` dBFS and followed by `pause` seconds of silence, the last
+    included (GPT-SoVITS's fragment_interval); the returned and the saved audio include the pauses.
     top_k (1..64), top_p (0 < p <= 1, nucleus sampling), temperature (> 0), repetition_penalty
     (> 0), seed: GPT-SoVITS's sampling controls; None keeps the field of `sampler` (or, without
     one, of the character's sampler), a value overrides it on a copy.  ValueError for a bad value."""
-    opts = vocoder_options(speed, sample_rate, False, loudness, peak)
+    opts = vocoder_options(speed, sample_rate, False, loudness, peak, pause, trim)
     out_rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
     fields = _sampling(top_k, top_p, temperature, repetition_penalty, seed)
     if character_name not in _reference_audios:
@@ -436,13 +440,15 @@ async def tts_async(character_name: str, text: str, play: bool = False, split_se
                     top_k: Optional[int] = None, top_p: Optional[float] = None,
                     temperature: Optional[float] = None, repetition_penalty: Optional[float] = None,
                     seed: Optional[int] = None, sample_rate: Optional[int] = None,
-                    loudness: Optional[float] = None, peak: Optional[float] = None) -> AsyncIterator[bytes]:
+                    loudness: Optional[float] = None, peak: Optional[float] = None,
+                    pause: Optional[float] = None, trim: Optional[float] = None) -> AsyncIterator[bytes]:
     """Internal.py:193-262: yields one raw 16-bit PCM chunk per sentence as soon as it
     is synthesized (TTSPlayer chunk callback), the engine running off the event loop.
-    speed, sampler, the sampling keywords, sample_rate and loudness / peak: as for tts.  With a
+    speed, sampler, the sampling keywords, sample_rate, loudness / peak and pause / trim: as for
+    tts (a chunk is a joined sentence, its pause included).  With a
     sample_rate the chunks are the int16 samples at that rate as the GPU's output stage wrote
     them (32000 gives the bytes of the call without it); None: converted on the host."""
-    opts = vocoder_options(speed, sample_rate, sample_rate is not None, loudness, peak)
+    opts = vocoder_options(speed, sample_rate, sample_rate is not None, loudness, peak, pause, trim)
     out_rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
     fields = _sampling(top_k, top_p, temperature, repetition_penalty, seed)
     if character_name not in _reference_audios:

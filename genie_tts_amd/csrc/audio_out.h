@@ -28,6 +28,12 @@ struct AudioOutItem {
     int rate;           // index into AudioRates
     int format;         // 0 float32, 1 int16
     const float* gain;  // device scalar of the loudness stage: y * gain before the conversion; null: none
+    // The join stage's device record {begin, end, n_speech, n_out} (join.h); null: none, and the
+    // fields above hold.  With it the item is src[begin, end) alone, n_speech samples, followed by
+    // zeros up to the record's n_out; n_out above is then the host's upper bound.
+    const int32_t* span;
+    int pause_n;        // samples of silence behind the speech (in the record's n_out); 0 without span
+    int pad;
 };
 
 int audio_rate_index(int out_rate);              // 0 -> 32000; -1: unsupported

@@ -35,25 +35,36 @@ __global__ __launch_bounds__(AO_TILE) void k_audio_out(AudioRates R, const Audio
     __shared__ float xs[AO_WIN];
     const AudioOutItem it = items[blockIdx.y];
     const int k0 = blockIdx.x * AO_TILE;
-    if (k0 >= it.n_out) return;
+    // With a span record (join.hip) the item is src[begin, end) alone, n_speech outputs, and the
+    // pause's zeros up to n_out; all four are read here, on the device.
+    const float* __restrict__ src = it.src;
+    int n_in = it.n_in, n_out = it.n_out, n_speech = it.n_out;
+    if (it.span) {
+        const int begin = it.span[0], end = it.span[1];
+        src += begin;
+        n_in = end - begin;
+        n_speech = it.span[2];
+        n_out = min(it.span[3], it.n_out);
+    }
+    if (k0 >= n_out) return;
     const int k = k0 + (int)threadIdx.x;
     const int up = R.up[it.rate], down = R.down[it.rate];
     float y = 0.f;
-    if (up == down) {   // 32000: a copy (n_out == n_in)
-        if (k < it.n_out) y = it.src[k];
-    } else {
+    if (up == down) {   // 32000: a copy (n_speech == n_in)
+        if (k < n_speech) y = src[k];
+    } else if (k0 < n_speech) {   // (the whole block: a tile of the pause alone stages nothing)
         const int half = R.half[it.rate], q = R.q[it.rate];
         const float* __restrict__ tab = R.tab[it.rate];
-        const int k1 = min(k0 + AO_TILE, it.n_out) - 1;   // the tile's last output
+        const int k1 = min(k0 + AO_TILE, n_speech) - 1;   // the tile's last output
         const long long lo = ((long long)k0 * down + half) / up - (q - 1);
         const long long hi = ((long long)k1 * down + half) / up;
         const int win = min((int)(hi - lo + 1), AO_WIN);   // (<= AO_WIN for every supported rate)
         for (int i = threadIdx.x; i < win; i += AO_TILE) {
             const long long n = lo + i;
-            xs[i] = n >= 0 && n < it.n_in ? it.src[n] : 0.f;
+            xs[i] = n >= 0 && n < n_in ? src[n] : 0.f;
         }
         __syncthreads();
-        if (k < it.n_out) {
+        if (k < n_speech) {
             const long long t = (long long)k * down + half;
             const long long n1 = t / up;
             const float* __restrict__ c = tab + (size_t)(t - n1 * up) * q;
@@ -61,8 +72,9 @@ __global__ __launch_bounds__(AO_TILE) void k_audio_out(AudioRates R, const Audio
             for (int i = 0; i < q; ++i) y = fmaf(c[i], x[i], y);
         }
     }
-    if (k >= it.n_out) return;
-    if (it.gain) y = y * *it.gain;   // loudness normalisation: one rounded multiply behind the chain
+    if (k >= n_out) return;
+    if (k >= n_speech) y = 0.f;   // the pause: +0.0f / int16 0, whatever the gain
+    else if (it.gain) y = y * *it.gain;   // loudness normalisation: one rounded multiply behind the chain
     if (it.format == 0) {
         ((float*)it.dst)[k] = y;
     } else {   // (x * 32767).astype(int16) of the reference, saturated
@@ -140,6 +152,7 @@ int gsv_engine::audio_out_init() {
         ao_rates.tab[i] = d;
     }
     if (int r = loudness_init()) return r;
+    if (int r = join_init()) return r;
     ao_tab = (AudioOutItem*)dalloc(sizeof(AudioOutItem) * AO_SLOTS);
     if (!ao_tab || hipHostMalloc((void**)&ao_pin, sizeof(AudioOutItem) * AO_SLOTS, hipHostMallocDefault) != hipSuccess)
         return set_error(GSV_E_HIP, "output stage item table");
@@ -163,8 +176,10 @@ int gsv_engine::audio_item(const gsv_vits_item& u, AudioOutItem* a) const {
 // that last read it has finished, which it has in practice (the wait is for the previous call's
 // stage, and a vocoder pass lies between two of them).  norm (null: none) lies beside items: the
 // entries with a target are measured first, one pass per launch (loudness.hip), and their
-// conversions read the gain from the measurement's slot on the device.
-int gsv_engine::audio_out(const AudioOutItem* items, const gsv_loudness* norm, int n, int region, hipStream_t s) {
+// conversions read the gain from the measurement's slot on the device.  The entries with a trim,
+// a pause or a span record go through the join stage the same way (join.hip): their conversions
+// read the span from the slot's record, and n_out of their table entry is the host's upper bound.
+int gsv_engine::audio_out(const AudioOutItem* items, const gsv_join* norm, int n, int region, hipStream_t s) {
     if (!ao_tab) return set_error(GSV_E_STATE, "output stage not initialised");
     const int base = region, cap = region == AO_BATCH_AT ? AO_BATCH : 1;   // (a region is its first slot)
     hipEvent_t ev = ao_ev[region];
@@ -174,12 +189,26 @@ int gsv_engine::audio_out(const AudioOutItem* items, const gsv_loudness* norm, i
         if (hipEventSynchronize(ev) != hipSuccess) return set_error(GSV_E_HIP, "output stage wait");
         int max_out = 0;
         std::vector<LoudItem> loud;
+        std::vector<JoinItem> join;
         for (int j = 0; j < m; ++j) {
             ao_pin[base + j] = items[i + j];
-            max_out = std::max(max_out, items[i + j].n_out);
+            if (norm && join_active(norm[i + j])) {
+                // its span goes into slot base + j's record, which this item's conversion reads on the device
+                const gsv_join& l = norm[i + j];
+                const AudioOutItem& a = items[i + j];
+                const int pause_n = join_pause_samples(RATES[a.rate], l.pause);
+                if (pause_n < 0) return set_error(GSV_E_ARG, "pause: 0 .. 5 seconds");
+                join.resize(m, JoinItem{nullptr, nullptr, nullptr, 0.0, -1, 0, 1, 1, 0, 0});
+                join[j] = JoinItem{a.src, l.span, nullptr, l.trim != 0.f ? std::pow(10.0, (double)l.trim / 10.0) : 0.0,
+                                   a.n_in, l.trim != 0.f, ao_rates.up[a.rate], ao_rates.down[a.rate], pause_n, 0};
+                ao_pin[base + j].span = jn_ws.span + (size_t)(base + j) * JN_SPAN;
+                ao_pin[base + j].pause_n = pause_n;
+                ao_pin[base + j].n_out += pause_n;
+            }
+            max_out = std::max(max_out, ao_pin[base + j].n_out);
             if (!norm || norm[i + j].target == 0.f) continue;
             // measured into slot base + j, whose gain this item's conversion reads on the device
-            const gsv_loudness& l = norm[i + j];
+            const gsv_join& l = norm[i + j];
             loud.resize(m, LoudItem{nullptr, nullptr, -1, 0.f, 1.f, 0});
             loud[j] = LoudItem{items[i + j].src, l.stats, items[i + j].n_in, l.target,
                                l.peak == 0.f ? 0.8912509381337456f : l.peak, 0};
@@ -187,6 +216,8 @@ int gsv_engine::audio_out(const AudioOutItem* items, const gsv_loudness* norm, i
         }
         if (!loud.empty())
             if (int r = loudness_measure(loud.data(), m, base, s)) return r;
+        if (!join.empty())
+            if (int r = join_measure(join.data(), m, base, s)) return r;
         hipMemcpyAsync(ao_tab + base, ao_pin + base, sizeof(AudioOutItem) * m, hipMemcpyHostToDevice, s);
         audio_out_launch(ao_rates, ao_tab + base, m, max_out, s);
         hipEventRecord(ev, s);
@@ -195,9 +226,9 @@ int gsv_engine::audio_out(const AudioOutItem* items, const gsv_loudness* norm, i
 }
 
 // The items of a vocoder call that carry `out`, converted from their final `audio`.
-int gsv_engine::audio_out_items(const gsv_vits_item* it, const gsv_loudness* norm, int n, int region, hipStream_t s) {
+int gsv_engine::audio_out_items(const gsv_vits_item* it, const gsv_join* norm, int n, int region, hipStream_t s) {
     std::vector<AudioOutItem> a;
-    std::vector<gsv_loudness> l;
+    std::vector<gsv_join> l;
     for (int i = 0; i < n; ++i) {
         if (!it[i].out) continue;
         a.emplace_back();
@@ -212,19 +243,23 @@ extern "C" int gsv_audio_samples(int32_t n_in, int32_t out_rate) {
     return n < 0 || n > INT32_MAX ? GSV_E_ARG : (int)n;
 }
 
-// The output stage alone on one buffer, its arguments checked first; l: null, or the target to bring it to.
-static int audio_entry(gsv_engine* eng, const float* audio_32k, int32_t n_in, const gsv_loudness* l, int32_t out_rate,
-                       int32_t out_format, void* out, void* stream) {
+// The output stage alone on one buffer, its arguments checked first; l: null, or the target to bring it
+// to (needed when `target`) and the join spec.
+static int audio_entry(gsv_engine* eng, const float* audio_32k, int32_t n_in, const gsv_join* l, bool target,
+                       int32_t out_rate, int32_t out_format, void* out, void* stream) {
     if (!eng) return set_error(GSV_E_ARG, "null engine");
     const int rate = audio_rate_index(out_rate), n_out = gsv_audio_samples(n_in, out_rate);
     if (rate < 0 || n_out < 0) return set_error(GSV_E_ARG, "out_rate: 8000, 16000, 22050, 24000, 32000, 44100 or 48000");
     if (out_format < 0 || out_format > 1) return set_error(GSV_E_ARG, "out_format: 0 (float32) or 1 (int16)");
     if (l) {
-        if (l->target == 0.f) return set_error(GSV_E_ARG, "loudness target: -50 .. -5 LUFS");
-        if (int r = check_loudness(*l)) return r;
-        if (n_in > LD_MAX_N) return set_error(GSV_E_ARG, "loudness: more than 640 * 4096 samples");
+        if (target && l->target == 0.f) return set_error(GSV_E_ARG, "loudness target: -50 .. -5 LUFS");
+        if (int r = check_loudness(gsv_loudness{l->target, l->peak, l->stats})) return r;
+        if (l->target != 0.f && n_in > LD_MAX_N) return set_error(GSV_E_ARG, "loudness: more than 640 * 4096 samples");
+        if (int r = check_join(*l)) return r;
+        if (l->trim != 0.f && n_in > JN_MAX_N) return set_error(GSV_E_ARG, "trim: more than 640 * 4096 samples");
     }
     if (n_in > 0 && (!audio_32k || !out)) return set_error(GSV_E_ARG, "null audio buffer");
+    if (l && l->pause != 0.f && !out) return set_error(GSV_E_ARG, "null audio buffer");
     hipSetDevice(eng->device);
     StreamScope sc(eng, stream);
     const AudioOutItem a{audio_32k, out, n_in, n_out, rate, out_format, nullptr};
@@ -233,11 +268,16 @@ static int audio_entry(gsv_engine* eng, const float* audio_32k, int32_t n_in, co
 
 extern "C" int gsv_audio_convert(gsv_engine* eng, const float* audio_32k, int32_t n_in, int32_t out_rate,
                                  int32_t out_format, void* out, void* stream) {
-    return audio_entry(eng, audio_32k, n_in, nullptr, out_rate, out_format, out, stream);
+    return audio_entry(eng, audio_32k, n_in, nullptr, false, out_rate, out_format, out, stream);
 }
 
 extern "C" int gsv_audio_normalize(gsv_engine* eng, const float* audio_32k, int32_t n_in, float target, float peak,
                                    int32_t out_rate, int32_t out_format, void* out, float* stats, void* stream) {
-    const gsv_loudness l{target, peak, stats};
-    return audio_entry(eng, audio_32k, n_in, &l, out_rate, out_format, out, stream);
+    const gsv_join l{target, peak, stats, 0.f, 0.f, nullptr};
+    return audio_entry(eng, audio_32k, n_in, &l, true, out_rate, out_format, out, stream);
+}
+
+extern "C" int gsv_audio_join(gsv_engine* eng, const float* audio_32k, int32_t n_in, const gsv_join* join,
+                              int32_t out_rate, int32_t out_format, void* out, void* stream) {
+    return audio_entry(eng, audio_32k, n_in, join, false, out_rate, out_format, out, stream);
 }

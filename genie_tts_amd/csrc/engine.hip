@@ -157,6 +157,7 @@ gsv_engine::~gsv_engine() {
     for (hipEvent_t e : ao_ev)
         if (e) hipEventDestroy(e);
     if (lo_pin) hipHostFree(lo_pin);
+    if (jn_pin) hipHostFree(jn_pin);
     for (hipEvent_t e : lo_ev)
         if (e) hipEventDestroy(e);
     if (res_pin) hipHostFree(res_pin);

@@ -19,10 +19,14 @@
 #include "vits.h"
 #include "audio_out.h"
 #include "loudness.h"
+#include "join.h"
 
 namespace gsv {
 int set_error(int code, const std::string& msg);
 int check_loudness(const gsv_loudness& l);   // target 0 (off) or in [-50, -5], peak 0 or in (0, 1]
+int check_join(const gsv_join& j);           // trim 0 (off) or in [-80, -20], pause in [0, 5]
+bool join_active(const gsv_join& j);         // a trim, a pause or a span record asked for
+int join_pause_samples(int out_rate, float pause);   // (int)((double)rate * (double)pause); -1: bad rate or pause
 int check_sampler(const gsv_sampler* s);   // top_k in [1, 64], top_p in (0, 1] or 0 (unset)
 inline float norm_top_p(float p) { return p == 0.f ? 1.f : p; }   // gsv_sampler.top_p: 0 means 1
 int hip_error(const std::string& what, hipError_t e);   // GSV_E_HIP, the message naming the HIP error
@@ -467,7 +471,7 @@ struct gsv_engine {
     int* vflags = nullptr;
     int* vflags_host = nullptr;
     int vflag_cap = 0;
-    int vits_decode_batch(int n, const gsv_vits_item* it, const gsv_loudness* norm, float noise_scale, hipStream_t s);
+    int vits_decode_batch(int n, const gsv_vits_item* it, const gsv_join* norm, float noise_scale, hipStream_t s);
     // overlapped batch (gsv_vits_decode_batch_async): issued by lane threads that may still
     // run when the call returns; vits_batch_finish joins
     std::vector<gsv_vits_item> vb_items;
@@ -511,7 +515,7 @@ struct gsv_engine {
     gsv_vits_item vcall{};
     float vcall_scale = 0.f;
     int set_vocoder_cus(int K);
-    int vits_async(const gsv_vits_item& u, const gsv_loudness* norm, float noise_scale, hipStream_t caller);
+    int vits_async(const gsv_vits_item& u, const gsv_join* norm, float noise_scale, hipStream_t caller);
     int vits_wait(hipStream_t caller);
     int vits_launch_queued(hipStream_t s = nullptr);
     hipStream_t vlast = nullptr;       // stream the pending vocoder call was launched on
@@ -558,8 +562,8 @@ struct gsv_engine {
     int audio_out_init();
     int audio_item(const gsv_vits_item& u, gsv::AudioOutItem* a) const;   // GSV_E_ARG: bad rate / format / speed
     // norm (null: none): [n] beside items; an entry with a target is measured first and its gain applied
-    int audio_out(const gsv::AudioOutItem* items, const gsv_loudness* norm, int n, int region, hipStream_t s);
-    int audio_out_items(const gsv_vits_item* it, const gsv_loudness* norm, int n, int region, hipStream_t s);
+    int audio_out(const gsv::AudioOutItem* items, const gsv_join* norm, int n, int region, hipStream_t s);
+    int audio_out_items(const gsv_vits_item* it, const gsv_join* norm, int n, int region, hipStream_t s);
     // ---- loudness stage (loudness.hip): one workspace slot per slot of the output stage's item table
     gsv::LoudFilter lo_filter{};
     gsv::LoudWorkspace lo_ws{};
@@ -568,8 +572,14 @@ struct gsv_engine {
     hipEvent_t lo_ev[3] = {};
     int loudness_init();
     int loudness_measure(const gsv::LoudItem* items, int m, int region, hipStream_t s);
-    gsv_loudness vcall_norm{};             // of the overlapped vocoder call (target 0: none)
-    std::vector<gsv_loudness> vb_norm;     // of the running batch (empty: none)
+    gsv_join vcall_norm{};                 // of the overlapped vocoder call (all zero: none)
+    std::vector<gsv_join> vb_norm;         // of the running batch (empty: none)
+    // ---- join stage (join.hip): edge-silence trim and pause; slots, regions and events as above
+    gsv::JoinWorkspace jn_ws{};
+    gsv::JoinItem* jn_tab = nullptr;   // [AO_SLOTS] device item table
+    gsv::JoinItem* jn_pin = nullptr;   // its pinned source
+    int join_init();
+    int join_measure(const gsv::JoinItem* items, int m, int region, hipStream_t s);
 };
 
 namespace gsv {

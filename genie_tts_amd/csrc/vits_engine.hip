@@ -718,7 +718,7 @@ int gsv_engine::set_vocoder_cus(int K) {
 // The call is queued, not launched: its ~400 launches are issued by the next
 // T2S generate right after the persistent decode kernel (vits_launch_queued), so
 // the host enqueues them while the GPU decodes instead of delaying that T2S.
-int gsv_engine::vits_async(const gsv_vits_item& u, const gsv_loudness* norm, float noise_scale, hipStream_t caller) {
+int gsv_engine::vits_async(const gsv_vits_item& u, const gsv_join* norm, float noise_scale, hipStream_t caller) {
     if (!vstream) return set_error(GSV_E_STATE, "overlapped vocoder: set option vocoder_cus first");
     if (int r = vits_wait(nullptr)) return r;
     if (vb_active)
@@ -730,7 +730,7 @@ int gsv_engine::vits_async(const gsv_vits_item& u, const gsv_loudness* norm, flo
     }
     hipEventRecord(vev_in, caller);   // the inputs are ready in the caller's stream order here
     vcall = u;
-    vcall_norm = norm ? *norm : gsv_loudness{};
+    vcall_norm = norm ? *norm : gsv_join{};
     vcall_scale = noise_scale;
     vqueued = true;
     return 0;
@@ -749,7 +749,7 @@ int gsv_engine::vits_launch_queued(hipStream_t s) {
                                  vcall_scale, u.audio, s, use_convh ? vovf : nullptr, timing, u.speed))
         return r;
     // on the vocoder's stream, behind its pass
-    if (int r = audio_out_items(&u, vcall_norm.target != 0.f ? &vcall_norm : nullptr, 1, AO_ASYNC, s)) return r;
+    if (int r = audio_out_items(&u, vcall_norm.target != 0.f || join_active(vcall_norm) ? &vcall_norm : nullptr, 1, AO_ASYNC, s)) return r;
     if (use_convh) hipMemcpyAsync(vovf_host, vovf, 4, hipMemcpyDeviceToHost, s);
     hipEventRecord(vev_done, s);
     vpending = true;
@@ -774,7 +774,7 @@ int gsv_engine::vits_wait(hipStream_t caller) {
                                      timing, u.speed))
             return r;
         // `out` (and its loudness) from the re-run's audio
-        if (int r = audio_out_items(&u, vcall_norm.target != 0.f ? &vcall_norm : nullptr, 1, AO_ASYNC, vlast)) return r;
+        if (int r = audio_out_items(&u, vcall_norm.target != 0.f || join_active(vcall_norm) ? &vcall_norm : nullptr, 1, AO_ASYNC, vlast)) return r;
         hipEventRecord(vev_done, vlast);
         if (hipEventSynchronize(vev_done) != hipSuccess) return set_error(GSV_E_HIP, "overlapped vocoder re-run");
     }
@@ -1167,7 +1167,7 @@ int gsv_engine::vits_front(VitsWorkspace& W, const int64_t* text_seq, int n_text
 // workspace), so up to K vocoder chains -- each a few hundred small launches that
 // under-fill the chip -- overlap on the GPU.  Each utterance has its own overflow
 // flag; after the join, flagged utterances are decoded again on the f32 path.
-int gsv_engine::vits_decode_batch(int n, const gsv_vits_item* it, const gsv_loudness* norm, float noise_scale,
+int gsv_engine::vits_decode_batch(int n, const gsv_vits_item* it, const gsv_join* norm, float noise_scale,
                                   hipStream_t s) {
     if (n <= 0) return 0;
     if (vb_active)   // an overlapped batch shares the lanes: finish it first
@@ -1690,19 +1690,21 @@ static bool vits_item_ok(const gsv_vits_item& u) {
 
 extern "C" int gsv_vits_frames(int32_t n_sem, float speed) { return vits_frames(n_sem, speed); }
 
-// The loudness specs beside items: each valid, and an item with a target has `out`.
-static int vits_norm_ok(const gsv_vits_item* items, const gsv_loudness* norm, int n) {
+// The specs beside items: each valid, and an item with a target, a trim or a pause has `out`.
+static int vits_norm_ok(const gsv_vits_item* items, const gsv_join* norm, int n) {
     for (int i = 0; norm && i < n; ++i) {
-        if (int r = check_loudness(norm[i])) return r;
+        if (int r = check_loudness(gsv_loudness{norm[i].target, norm[i].peak, norm[i].stats})) return r;
         if (norm[i].target != 0.f && !items[i].out)
             return set_error(GSV_E_ARG, "loudness target on an item without `out`");
+        if (int r = check_join(norm[i])) return r;
+        if (join_active(norm[i]) && !items[i].out) return set_error(GSV_E_ARG, "pause or trim on an item without `out`");
     }
     return 0;
 }
 
 // What the four vocoder entries check before anything runs.  one: a single item, checked before
 // the engine's state; else a batch of at least min_n, checked after it, its errors naming the item.
-static int vits_entry_ok(gsv_engine* eng, const gsv_vits_item* items, const gsv_loudness* norm, int n, bool one,
+static int vits_entry_ok(gsv_engine* eng, const gsv_vits_item* items, const gsv_join* norm, int n, bool one,
                          int min_n = 0) {
     if (!eng) return set_error(GSV_E_ARG, "null engine");
     auto args = [&]() -> int {
@@ -1720,42 +1722,67 @@ static int vits_entry_ok(gsv_engine* eng, const gsv_vits_item* items, const gsv_
     return one ? 0 : args();
 }
 
-extern "C" int gsv_vits_decode_item_norm(gsv_engine* eng, const gsv_vits_item* item, const gsv_loudness* norm,
+// The `_norm` entries' specs as the `_join` entries take them (no trim, no pause, no span record).
+static std::vector<gsv_join> norm_as_join(const gsv_loudness* norm, int n) {
+    std::vector<gsv_join> j;
+    for (int i = 0; norm && i < n; ++i) j.push_back(gsv_join{norm[i].target, norm[i].peak, norm[i].stats, 0.f, 0.f, nullptr});
+    return j;
+}
+
+extern "C" int gsv_vits_decode_item_join(gsv_engine* eng, const gsv_vits_item* item, const gsv_join* join,
                                          float noise_scale, void* stream) {
-    if (int r = vits_entry_ok(eng, item, norm, 1, true)) return r;
+    if (int r = vits_entry_ok(eng, item, join, 1, true)) return r;
     StreamScope sc(eng, stream);
     const gsv_vits_item& u = *item;
     if (int r = eng->vits_decode(u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge, u.ge_adv,
                                  u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0,
                                  noise_scale, u.audio, sc.st(), u.speed))
         return r;
-    return eng->audio_out_items(&u, norm, 1, gsv_engine::AO_SYNC, sc.st());
+    return eng->audio_out_items(&u, join, 1, gsv_engine::AO_SYNC, sc.st());
+}
+
+extern "C" int gsv_vits_decode_item_norm(gsv_engine* eng, const gsv_vits_item* item, const gsv_loudness* norm,
+                                         float noise_scale, void* stream) {
+    const std::vector<gsv_join> j = norm_as_join(norm, 1);
+    return gsv_vits_decode_item_join(eng, item, norm ? j.data() : nullptr, noise_scale, stream);
 }
 
 extern "C" int gsv_vits_decode_item(gsv_engine* eng, const gsv_vits_item* item, float noise_scale, void* stream) {
-    return gsv_vits_decode_item_norm(eng, item, nullptr, noise_scale, stream);
+    return gsv_vits_decode_item_join(eng, item, nullptr, noise_scale, stream);
+}
+
+extern "C" int gsv_vits_decode_batch_join(gsv_engine* eng, int32_t n, const gsv_vits_item* items,
+                                          const gsv_join* join, float noise_scale, void* stream) {
+    if (int r = vits_entry_ok(eng, items, join, n, false)) return r;
+    StreamScope sc(eng, stream);
+    return eng->vits_decode_batch(n, items, join, noise_scale, sc.st());
 }
 
 extern "C" int gsv_vits_decode_batch_norm(gsv_engine* eng, int32_t n, const gsv_vits_item* items,
                                           const gsv_loudness* norm, float noise_scale, void* stream) {
-    if (int r = vits_entry_ok(eng, items, norm, n, false)) return r;
-    StreamScope sc(eng, stream);
-    return eng->vits_decode_batch(n, items, norm, noise_scale, sc.st());
+    const std::vector<gsv_join> j = norm_as_join(norm, n);
+    return gsv_vits_decode_batch_join(eng, n, items, norm ? j.data() : nullptr, noise_scale, stream);
 }
 
 extern "C" int gsv_vits_decode_batch(gsv_engine* eng, int32_t n, const gsv_vits_item* items, float noise_scale,
                                      void* stream) {
-    return gsv_vits_decode_batch_norm(eng, n, items, nullptr, noise_scale, stream);
+    return gsv_vits_decode_batch_join(eng, n, items, nullptr, noise_scale, stream);
+}
+
+extern "C" int gsv_vits_decode_async_join(gsv_engine* eng, const gsv_vits_item* item, const gsv_join* join,
+                                          float noise_scale, void* stream) {
+    if (int r = vits_entry_ok(eng, item, join, 1, true)) return r;
+    return eng->vits_async(*item, join, noise_scale, (hipStream_t)stream);
 }
 
 extern "C" int gsv_vits_decode_async_norm(gsv_engine* eng, const gsv_vits_item* item, const gsv_loudness* norm,
                                           float noise_scale, void* stream) {
-    if (int r = vits_entry_ok(eng, item, norm, 1, true)) return r;
-    return eng->vits_async(*item, norm, noise_scale, (hipStream_t)stream);
+    const std::vector<gsv_join> j = norm_as_join(norm, 1);
+    return gsv_vits_decode_async_join(eng, item, norm ? j.data() : nullptr, noise_scale, stream);
 }
 
 extern "C" int gsv_vits_decode_async(gsv_engine* eng, const gsv_vits_item* item, float noise_scale, void* stream) {
-    return gsv_vits_decode_async_norm(eng, item, nullptr, noise_scale, stream);
+    return gsv_vits_decode_async_join(eng, item, nullptr, noise_scale, stream);
 }
 
 extern "C" int gsv_vits_wait(gsv_engine* eng, void* stream) {
@@ -1764,21 +1791,27 @@ extern "C" int gsv_vits_wait(gsv_engine* eng, void* stream) {
     return eng->vits_wait((hipStream_t)stream);
 }
 
-extern "C" int gsv_vits_decode_batch_async_norm(gsv_engine* eng, int32_t n, const gsv_vits_item* items,
-                                                const gsv_loudness* norm, float noise_scale, void* stream) {
-    if (int r = vits_entry_ok(eng, items, norm, n, false, 1)) return r;
+extern "C" int gsv_vits_decode_batch_async_join(gsv_engine* eng, int32_t n, const gsv_vits_item* items,
+                                                const gsv_join* join, float noise_scale, void* stream) {
+    if (int r = vits_entry_ok(eng, items, join, n, false, 1)) return r;
     if (int r = eng->vits_batch_finish(nullptr)) return r;
     if (int r = eng->vits_wait(nullptr)) return r;
     eng->vb_items.assign(items, items + n);
-    eng->vb_norm.assign(norm, norm ? norm + n : norm);
+    eng->vb_norm.assign(join, join ? join + n : join);
     // ordered after the caller's stream only: the engine stream stays free for the T2S
     // of the next batch, which runs beside this one
     return eng->vits_batch_launch(noise_scale, (hipStream_t)stream, false);
 }
 
+extern "C" int gsv_vits_decode_batch_async_norm(gsv_engine* eng, int32_t n, const gsv_vits_item* items,
+                                                const gsv_loudness* norm, float noise_scale, void* stream) {
+    const std::vector<gsv_join> j = norm_as_join(norm, n);
+    return gsv_vits_decode_batch_async_join(eng, n, items, norm ? j.data() : nullptr, noise_scale, stream);
+}
+
 extern "C" int gsv_vits_decode_batch_async(gsv_engine* eng, int32_t n, const gsv_vits_item* items,
                                            float noise_scale, void* stream) {
-    return gsv_vits_decode_batch_async_norm(eng, n, items, nullptr, noise_scale, stream);
+    return gsv_vits_decode_batch_async_join(eng, n, items, nullptr, noise_scale, stream);
 }
 
 extern "C" int gsv_vits_batch_wait(gsv_engine* eng, void* stream) {

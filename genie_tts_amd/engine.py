@@ -91,6 +91,13 @@ class Loudness(ctypes.Structure):
     _fields_ = [("target", ctypes.c_float), ("peak", ctypes.c_float), ("stats", ctypes.c_void_p)]
 
 
+class Join(ctypes.Structure):
+    """gsv_join: gsv_loudness's fields plus the trim threshold (dBFS, 0: off), the pause (seconds)
+    and the device span record int32[4] {begin, end, n_speech, n_out} (0: not wanted)."""
+    _fields_ = [("target", ctypes.c_float), ("peak", ctypes.c_float), ("stats", ctypes.c_void_p),
+                ("trim", ctypes.c_float), ("pause", ctypes.c_float), ("span", ctypes.c_void_p)]
+
+
 class Sampler(ctypes.Structure):
     _fields_ = [
         ("top_k", ctypes.c_int32), ("temperature", ctypes.c_float),
@@ -339,6 +346,15 @@ def lib():
         L.gsv_audio_loudness.argtypes = [vp, vp, i32, vp, vp]
         L.gsv_audio_normalize.argtypes = [vp, vp, i32, ctypes.c_float, ctypes.c_float, i32, i32, vp, vp, vp]
         L.gsv_debug_loudness_hops.argtypes = [vp, vp, i32, vp, vp]
+        jnp = ctypes.POINTER(Join)
+        L.gsv_join_pause_samples.argtypes = [i32, ctypes.c_float]
+        L.gsv_join_samples.argtypes = [i32, i32, ctypes.c_float]
+        L.gsv_vits_decode_item_join.argtypes = [vp, ctypes.POINTER(VitsItem), jnp, ctypes.c_float, vp]
+        L.gsv_vits_decode_batch_join.argtypes = [vp, i32, ctypes.POINTER(VitsItem), jnp, ctypes.c_float, vp]
+        L.gsv_vits_decode_batch_async_join.argtypes = [vp, i32, ctypes.POINTER(VitsItem), jnp, ctypes.c_float, vp]
+        L.gsv_vits_decode_async_join.argtypes = [vp, ctypes.POINTER(VitsItem), jnp, ctypes.c_float, vp]
+        L.gsv_audio_join.argtypes = [vp, vp, i32, jnp, i32, i32, vp, vp]
+        L.gsv_debug_join_frames.argtypes = [vp, vp, i32, vp, vp]
         L.gsv_vits_batch_wait.argtypes = [vp, vp]
         L.gsv_t2s_prefetch.argtypes = [vp, ctypes.POINTER(Utt), ctypes.POINTER(Sampler), vp]
         L.gsv_t2s_generate_start.argtypes = [vp, ctypes.POINTER(Utt), ctypes.POINTER(Sampler), vp]
@@ -411,6 +427,8 @@ EXPORTED = (
     "gsv_loudness_coeffs", "gsv_vits_decode_item_norm", "gsv_vits_decode_batch_norm",
     "gsv_vits_decode_batch_async_norm", "gsv_vits_decode_async_norm", "gsv_audio_loudness",
     "gsv_audio_normalize", "gsv_debug_loudness_hops", "gsv_ge_mix", "gsv_ge_project",
+    "gsv_join_pause_samples", "gsv_join_samples", "gsv_vits_decode_item_join", "gsv_vits_decode_batch_join",
+    "gsv_vits_decode_batch_async_join", "gsv_vits_decode_async_join", "gsv_audio_join", "gsv_debug_join_frames",
 )
 
 
@@ -505,10 +523,52 @@ def check_loudness(loudness=None, peak=None) -> dict:
     return out if loudness is not None else {}
 
 
-VOCODER_OPTIONS = ("speed", "sample_rate", "pcm16", "loudness", "peak")
+JOIN_FRAME = 320          # GSV_JOIN_FRAME: samples of a trim frame (10 ms at 32 kHz)
+JOIN_GUARD = 640          # GSV_JOIN_GUARD: samples kept on either side of the active frames (20 ms)
 
 
-def vocoder_options(speed=None, sample_rate=None, pcm16=False, loudness=None, peak=None) -> dict:
+def check_join(pause=None, trim=None) -> dict:
+    """The join keys of a vocoder call, validated: `pause` seconds of silence behind the sentence
+    within [0, 5] (None or 0: none), `trim` a threshold in dBFS within [-80, -20] (None: nothing
+    is cut).  ValueError otherwise.  Nothing when neither is given, and the call is then today's."""
+    out = {}
+    for name, v, lo, hi in (("pause", pause, 0.0, 5.0), ("trim", trim, -80.0, -20.0)):
+        if v is None:
+            continue
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or \
+                not math.isfinite(float(v)) or not lo <= float(v) <= hi:
+            raise ValueError(f"pause must be seconds within [0, 5], not {v!r}" if name == "pause"
+                             else f"trim must be a threshold in dBFS within [-80, -20], not {v!r}")
+        if name == "trim" or float(v) != 0.0:
+            out[name] = float(v)
+    return out
+
+
+def join_pause_samples(sample_rate: int = 32000, pause: float = 0.0) -> int:
+    """Samples of `pause` seconds at sample_rate (gsv_join_pause_samples, the one place the count
+    is computed: (int)((double)rate * (double)(float32)pause))."""
+    audio_samples(0, sample_rate)
+    n = lib().gsv_join_pause_samples(int(sample_rate), ctypes.c_float(float(pause)))
+    if n < 0:
+        raise ValueError(f"pause must be seconds within [0, 5], not {pause!r}")
+    return n
+
+
+def join_samples(n: int, sample_rate: int = 32000, pause: float = 0.0) -> int:
+    """The most samples a joined item gives (gsv_join_samples): audio_samples(n, sample_rate)
+    plus the pause's; what its output buffer must hold."""
+    audio_samples(0, sample_rate)
+    m = lib().gsv_join_samples(int(n), int(sample_rate), ctypes.c_float(float(pause)))
+    if m < 0:
+        raise ValueError(f"no output length for {n!r} samples at {sample_rate!r} Hz with a pause of {pause!r}")
+    return m
+
+
+VOCODER_OPTIONS = ("speed", "sample_rate", "pcm16", "loudness", "peak", "pause", "trim")
+
+
+def vocoder_options(speed=None, sample_rate=None, pcm16=False, loudness=None, peak=None, pause=None,
+                    trim=None) -> dict:
     """The options of one vocoder call, validated (ValueError, before any GPU work), as the
     keywords of Engine.vits_decode / the keys of a vocoder item.  Only what differs from the
     call without options is returned, so nothing given is that call, with no extra keyword.
@@ -522,7 +582,11 @@ def vocoder_options(speed=None, sample_rate=None, pcm16=False, loudness=None, pe
       (within [-50, -5]; e.g. -16 for speech, EBU R 128's -23) on the GPU, in front of the
       conversion, the gain limited so that the 32 kHz sample peak stays under `peak` (linear,
       (0, 1]; None: -1 dBFS).  With loudness alone the audio is float32 at 32 kHz, normalised.
-      A `peak` without a `loudness` is validated and dropped."""
+      A `peak` without a `loudness` is validated and dropped.
+    pause / trim: the sentence join, on the GPU in the same stage.  `trim` (dBFS, -80 .. -20) cuts
+      the leading and trailing audio quieter than it, down to a guard of 20 ms; `pause` (seconds,
+      0 .. 5; GPT-SoVITS's `fragment_interval`) appends silence.  The result then has as many
+      samples as the span record says (Engine.vits_joined).  No key for a pause of None or 0."""
     out = {}
     if speed is not None:
         vits_frames(0, speed)
@@ -530,13 +594,17 @@ def vocoder_options(speed=None, sample_rate=None, pcm16=False, loudness=None, pe
             out["speed"] = float(speed)
     out.update(check_out_format(sample_rate, pcm16))
     out.update(check_loudness(loudness, peak))
+    out.update(check_join(pause, trim))
     return out
 
 
-def vocoder_options_each(n: int, speed=1.0, sample_rate=None, pcm16=False, loudness=None, peak=None) -> List[dict]:
+def vocoder_options_each(n: int, speed=1.0, sample_rate=None, pcm16=False, loudness=None, peak=None, pause=None,
+                         trim=None) -> List[dict]:
     """vocoder_options of n items, each option one value for all of them or one per item."""
-    cols = [[v] * n if v is None or np.ndim(v) == 0 else list(v) for v in (speed, sample_rate, pcm16, loudness, peak)]
-    for what, group in (("speed", cols[:1]), ("sample_rate / pcm16", cols[1:3]), ("loudness / peak", cols[3:])):
+    cols = [[v] * n if v is None or np.ndim(v) == 0 else list(v)
+            for v in (speed, sample_rate, pcm16, loudness, peak, pause, trim)]
+    for what, group in (("speed", cols[:1]), ("sample_rate / pcm16", cols[1:3]), ("loudness / peak", cols[3:5]),
+                        ("pause / trim", cols[5:])):
         if any(len(c) != n for c in group):
             raise ValueError(f"{what}: one value, or one per item")
     return [vocoder_options(*row) for row in zip(*cols)]
@@ -1082,28 +1150,35 @@ class Engine:
     def vits_decode(self, text_seq, pred_semantic, ref_audio=None, ge=None, ge_advanced=None,
                     eps=None, noise_scale: float = 0.5, noise_seed: Optional[int] = None, speed: float = 1.0,
                     sample_rate: Optional[int] = None, pcm16: bool = False, loudness: Optional[float] = None,
-                    peak: Optional[float] = None):
+                    peak: Optional[float] = None, pause: Optional[float] = None, trim: Optional[float] = None):
         """vits_fp32.onnx for one utterance.  Noise of z_p: eps (tensor/array [192, T']) if
         given, else the engine's Philox N(0,1) stream keyed by noise_seed if given, else zeros.
         speed, sample_rate / pcm16, loudness / peak: see vocoder_options.  With an output format or
         a loudness target the result is the output stage's tensor; the 32 kHz float32 audio is
-        self.vits_audio_32k[0] and the loudness stats (device float32 [4]) self.vits_loudness[0]."""
+        self.vits_audio_32k[0] and the loudness stats (device float32 [4]) self.vits_loudness[0].
+        pause / trim: the result is the joined sentence (vits_joined), its span self.vits_spans[0]."""
         item = dict(text_seq=text_seq, pred_semantic=pred_semantic, ref_audio=ref_audio, ge=ge,
                     ge_advanced=ge_advanced, speed=speed, sample_rate=sample_rate, pcm16=pcm16, loudness=loudness,
-                    peak=peak)
+                    peak=peak, pause=pause, trim=trim)
         if noise_seed is not None and eps is None:
             return self.vits_decode_batch([dict(item, noise_seed=noise_seed)], noise_scale)[0]
-        norm = []
-        it, keep, audio = self._vits_item(dict(item, eps=eps), norm)
+        norm, join = [], []
+        it, keep, audio = self._vits_item(dict(item, eps=eps), norm, join)
         ld, stats = norm[0]
-        _check(lib().gsv_vits_decode_item_norm(self.h, ctypes.byref(it), None if stats is None else ctypes.byref(ld),
-                                               ctypes.c_float(noise_scale), _stream()), "gsv_vits_decode_item_norm")
+        jn = self._join_specs(norm, join)
+        if jn is not None:
+            _check(lib().gsv_vits_decode_item_join(self.h, ctypes.byref(it), jn, ctypes.c_float(noise_scale),
+                                                   _stream()), "gsv_vits_decode_item_join")
+        else:
+            _check(lib().gsv_vits_decode_item_norm(self.h, ctypes.byref(it),
+                                                   None if stats is None else ctypes.byref(ld),
+                                                   ctypes.c_float(noise_scale), _stream()), "gsv_vits_decode_item_norm")
         self.vits_audio_32k = [keep[-1] if it.out else audio]
         self.vits_loudness = [stats]
-        return audio
+        return self.vits_joined([audio])[0]
 
     def audio_convert(self, audio, sample_rate: int = 32000, pcm16: bool = False, loudness: Optional[float] = None,
-                      peak: Optional[float] = None):
+                      peak: Optional[float] = None, pause: Optional[float] = None, trim: Optional[float] = None):
         """The output stage alone (gsv_audio_convert): 32 kHz float32 audio [n] -> its
         audio_samples(n, sample_rate) samples at sample_rate (one of SAMPLE_RATES; the polyphase
         resample of include/genie_engine.h, scipy.signal.resample_poly's default filter), as float32
@@ -1112,11 +1187,26 @@ class Engine:
         loudness / peak (gsv_audio_normalize): the audio is first measured by ITU-R BS.1770-4 and
         every sample multiplied, before the int16 conversion, by the gain that brings it to
         `loudness` LUFS, limited so that the 32 kHz sample peak stays under `peak` (linear, None:
-        -1 dBFS); self.vits_loudness[0] is then the device stats [loudness, peak, gain, blocks_kept]."""
+        -1 dBFS); self.vits_loudness[0] is then the device stats [loudness, peak, gain, blocks_kept].
+        pause / trim (gsv_audio_join; see vocoder_options): only the span of the audio above `trim`
+        dBFS is converted and `pause` seconds of zeros follow it; self.vits_spans[0] is then the
+        device span record [begin, end, n_speech, n_out] and the result has n_out samples."""
         t = self.torch
         a = self._dev(audio, t.float32).reshape(-1)
-        out = t.empty((audio_samples(a.numel(), sample_rate),), dtype=t.int16 if pcm16 else t.float32, device=self.dev)
         ld = check_loudness(loudness, peak)
+        jn = check_join(pause, trim)
+        if jn:
+            ps = jn.get("pause", 0.0)
+            out = t.empty((join_samples(a.numel(), sample_rate, ps),), dtype=t.int16 if pcm16 else t.float32,
+                          device=self.dev)
+            stats = t.empty((4,), dtype=t.float32, device=self.dev) if ld else None
+            spec = self._join_specs([(Loudness(ld["loudness"], ld.get("peak", 0.0), stats.data_ptr()) if ld
+                                      else Loudness(), stats)], [jn])
+            _check(lib().gsv_audio_join(self.h, _ptr(a), a.numel(), spec, int(sample_rate), int(bool(pcm16)),
+                                        _ptr(out), _stream()), "gsv_audio_join")
+            self.vits_loudness = [stats]
+            return self.vits_joined([out])[0]
+        out = t.empty((audio_samples(a.numel(), sample_rate),), dtype=t.int16 if pcm16 else t.float32, device=self.dev)
         if ld:
             stats = t.empty((4,), dtype=t.float32, device=self.dev)
             _check(lib().gsv_audio_normalize(self.h, _ptr(a), a.numel(), ctypes.c_float(ld["loudness"]),
@@ -1141,6 +1231,15 @@ class Engine:
         lufs, pk = stats[:2].cpu().tolist()
         return lufs, pk
 
+    def debug_join_frames(self, audio):
+        """gsv_debug_join_frames: the sum of squares of each 10 ms frame (the last may be partial),
+        device float64 [ceil(n / 320)]."""
+        t = self.torch
+        a = self._dev(audio, t.float32).reshape(-1)
+        e = t.empty(((a.numel() + JOIN_FRAME - 1) // JOIN_FRAME,), dtype=t.float64, device=self.dev)
+        _check(lib().gsv_debug_join_frames(self.h, _ptr(a), a.numel(), _ptr(e), _stream()), "gsv_debug_join_frames")
+        return e
+
     def debug_loudness_hops(self, audio):
         """gsv_debug_loudness_hops: the K-weighted energy of each full 100 ms hop, device [n // 3200]."""
         t = self.torch
@@ -1152,12 +1251,53 @@ class Engine:
 
     vits_audio_32k: list = []      # the 32 kHz float32 tensors of the last vocoder call, in item order
     vits_loudness: list = []       # its items' loudness stats (device float32 [4]; None: not normalised)
+    vits_spans: list = []          # its items' span records (device int32 [4]; None: not trimmed)
+    _vits_span_all = None          # the one tensor [items, 4] they are rows of
 
-    def _vits_item(self, it: dict, norm: Optional[list] = None):
+    def _join_specs(self, norm: list, join: list):
+        """The gsv_join array of a call from its items' (Loudness, stats) and join options (the
+        lists _vits_item fills), or None when no item has a pause or a trim: the call is then the
+        `_norm` one.  The span records of the items that trim are rows of one device tensor, so
+        vits_joined reads them in a single copy."""
+        t = self.torch
+        self.vits_spans, self._vits_span_all = [None] * len(join), None
+        if not any(join):
+            return None
+        rows = [i for i, j in enumerate(join) if "trim" in j]
+        if rows:
+            self._vits_span_all = t.empty((len(rows), 4), dtype=t.int32, device=self.dev)
+            for r, i in enumerate(rows):
+                self.vits_spans[i] = self._vits_span_all[r]
+        arr = (Join * len(join))()
+        for i, ((ld, _), j) in enumerate(zip(norm, join)):
+            sp = self.vits_spans[i]
+            arr[i] = Join(ld.target, ld.peak, ld.stats, j.get("trim", 0.0), j.get("pause", 0.0),
+                          0 if sp is None else sp.data_ptr())
+        return arr
+
+    def vits_joined(self, outs: Sequence):
+        """The results of the last vocoder call (after its wait) cut to their joined lengths: for an
+        item with `trim`, out[:n_out] of its span record -- all the records of the call in one
+        device-to-host copy; every other item as it is (with `pause` alone the length is known on
+        the host and nothing is read back)."""
+        if self._vits_span_all is None:
+            return list(outs)
+        rec = self._vits_span_all.cpu()
+        r, res = 0, []
+        for o, sp in zip(outs, self.vits_spans):
+            if sp is None:
+                res.append(o)
+            else:
+                res.append(o[:int(rec[r, 3])])
+                r += 1
+        return res
+
+    def _vits_item(self, it: dict, norm: Optional[list] = None, join: Optional[list] = None):
         """(VitsItem, tensors it points at, result tensor) of one vocoder call, its option keys
         resolved by vocoder_options.  With sample_rate / pcm16 / loudness the result is the output
         stage's tensor (the item's `out`), and the 32 kHz float32 audio, still written, is the last
-        of the kept tensors.  norm: a list that receives the item's (Loudness, stats tensor or None)."""
+        of the kept tensors.  norm: a list that receives the item's (Loudness, stats tensor or None);
+        join: one that receives its pause / trim options (empty: none)."""
         opts = vocoder_options(*(it.get(k) for k in VOCODER_OPTIONS))
         t = self.torch
         ts, sem = self._ids(it["text_seq"]), self._ids(it["pred_semantic"])
@@ -1186,10 +1326,16 @@ class Engine:
                          stats))
         elif target is not None:
             raise EngineError("loudness on an entry without a loudness spec")
+        jn = {k: opts[k] for k in ("pause", "trim") if k in opts}
+        if join is not None:
+            join.append(jn)
+        elif jn:
+            raise EngineError("pause / trim on an entry without a join spec")
         if opts.keys() <= {"speed"}:
             return item, [ts, sem, ra, g, ga, e], audio
         rate, pcm = opts.get("sample_rate", 32000), "pcm16" in opts
-        out = t.empty((audio_samples(640 * frames, rate),), dtype=t.int16 if pcm else t.float32, device=self.dev)
+        n_out = join_samples(640 * frames, rate, jn.get("pause", 0.0)) if jn else audio_samples(640 * frames, rate)
+        out = t.empty((n_out,), dtype=t.int16 if pcm else t.float32, device=self.dev)
         item.out_rate, item.out_format, item.out = rate, int(pcm), out.data_ptr()
         return item, [ts, sem, ra, g, ga, e, audio], out
 
@@ -1205,22 +1351,30 @@ class Engine:
         item (1280 G at speed 1), the output stage's where the item asks for it (one stage launch
         for the batch); self.vits_audio_32k then holds every item's 32 kHz audio."""
         arr, norm, keep, outs, a32 = self._vits_items(items)
-        _check(lib().gsv_vits_decode_batch_norm(self.h, len(items), arr, norm, ctypes.c_float(noise_scale),
-                                                _stream()), "gsv_vits_decode_batch_norm")
+        if isinstance(norm, ctypes.Array) and norm._type_ is Join:
+            _check(lib().gsv_vits_decode_batch_join(self.h, len(items), arr, norm, ctypes.c_float(noise_scale),
+                                                    _stream()), "gsv_vits_decode_batch_join")
+        else:
+            _check(lib().gsv_vits_decode_batch_norm(self.h, len(items), arr, norm, ctypes.c_float(noise_scale),
+                                                    _stream()), "gsv_vits_decode_batch_norm")
         self.vits_audio_32k = a32
-        return outs
+        return self.vits_joined(outs)
 
     def _vits_items(self, items: Sequence[dict]):
-        """The item array of a batch, its gsv_loudness array (None when no item has a target),
-        the kept tensors, the results and the 32 kHz tensors."""
+        """The item array of a batch, its gsv_loudness array (None when no item has a target; a
+        gsv_join array when an item has a pause or a trim), the kept tensors, the results and the
+        32 kHz tensors."""
         arr = (VitsItem * len(items))()
-        keep, outs, a32, norm = [], [], [], []
+        keep, outs, a32, norm, join = [], [], [], [], []
         for i, it in enumerate(items):
-            arr[i], k, audio = self._vits_item(it, norm)
+            arr[i], k, audio = self._vits_item(it, norm, join)
             keep += k
             outs.append(audio)
             a32.append(k[-1] if arr[i].out else audio)
         self.vits_loudness = [st for _, st in norm]
+        jn = self._join_specs(norm, join)
+        if jn is not None:
+            return arr, jn, keep + self.vits_loudness + [self._vits_span_all], outs, a32
         if not any(st is not None for st in self.vits_loudness):
             return arr, None, keep, outs, a32
         keep += self.vits_loudness
@@ -1229,10 +1383,15 @@ class Engine:
     def vits_decode_batch_async(self, items: Sequence[dict], noise_scale: float = 0.5):
         """vits_decode_batch without the join (gsv_vits_decode_batch_async): the lanes run
         beside whatever T2S is issued next.  Returns the audio tensors, valid after
-        vits_batch_wait()."""
+        vits_batch_wait(); with `trim`, vits_joined(them) then cuts them to their joined lengths."""
         arr, norm, keep, outs, a32 = self._vits_items(items)
-        _check(lib().gsv_vits_decode_batch_async_norm(self.h, len(items), arr, norm, ctypes.c_float(noise_scale),
-                                                      _stream()), "gsv_vits_decode_batch_async_norm")
+        if isinstance(norm, ctypes.Array) and norm._type_ is Join:
+            _check(lib().gsv_vits_decode_batch_async_join(self.h, len(items), arr, norm, ctypes.c_float(noise_scale),
+                                                          _stream()), "gsv_vits_decode_batch_async_join")
+        else:
+            _check(lib().gsv_vits_decode_batch_async_norm(self.h, len(items), arr, norm,
+                                                          ctypes.c_float(noise_scale), _stream()),
+                   "gsv_vits_decode_batch_async_norm")
         self.vits_audio_32k = a32
         # items and device buffers live until the wait -- also a previous batch's, which this
         # call only ordered behind the engine stream (its lanes may still read them)
@@ -1256,12 +1415,19 @@ class Engine:
     def vits_decode_async(self, item: dict, noise_scale: float = 0.5):
         """Start one vocoder call on the vocoder CUs (gsv_vits_decode_async) and return its
         audio tensor [640 T'], valid after vits_wait().  item as for vits_decode_batch."""
-        norm = []
-        it, keep, audio = self._vits_item(item, norm)
+        norm, join = [], []
+        it, keep, audio = self._vits_item(item, norm, join)
         ld, stats = norm[0]
-        _check(lib().gsv_vits_decode_async_norm(self.h, ctypes.byref(it), None if stats is None else ctypes.byref(ld),
-                                                ctypes.c_float(noise_scale), _stream()), "gsv_vits_decode_async_norm")
-        self._vits_keep = keep + [stats]   # device inputs stay alive until the call is finished
+        jn = self._join_specs(norm, join)
+        if jn is not None:
+            _check(lib().gsv_vits_decode_async_join(self.h, ctypes.byref(it), jn, ctypes.c_float(noise_scale),
+                                                    _stream()), "gsv_vits_decode_async_join")
+        else:
+            _check(lib().gsv_vits_decode_async_norm(self.h, ctypes.byref(it),
+                                                    None if stats is None else ctypes.byref(ld),
+                                                    ctypes.c_float(noise_scale), _stream()),
+                   "gsv_vits_decode_async_norm")
+        self._vits_keep = keep + [stats, self._vits_span_all]   # device inputs stay alive until the call is finished
         self.vits_loudness = [stats]
         self.vits_audio_32k = [keep[-1] if it.out else audio]
         return audio

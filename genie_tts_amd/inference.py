@@ -249,10 +249,11 @@ class GENIE:
             text_bert: Optional[np.ndarray] = None, g2p: Optional[Callable] = None,
             sampler: Optional[Sampler] = None, speed: float = 1.0, sample_rate: Optional[int] = None,
             pcm16: bool = False, loudness: Optional[float] = None,
-            peak: Optional[float] = None) -> Optional[np.ndarray]:
-        """speed, sample_rate / pcm16, loudness / peak: engine.vocoder_options (ValueError for a
-        bad value, before any GPU work); none given: the reference's audio."""
-        rate = vocoder_options(speed, sample_rate, pcm16, loudness, peak)
+            peak: Optional[float] = None, pause: Optional[float] = None,
+            trim: Optional[float] = None) -> Optional[np.ndarray]:
+        """speed, sample_rate / pcm16, loudness / peak, pause / trim: engine.vocoder_options
+        (ValueError for a bad value, before any GPU work); none given: the reference's audio."""
+        rate = vocoder_options(speed, sample_rate, pcm16, loudness, peak, pause, trim)
         if isinstance(text, str):
             if g2p is None:
                 raise ValueError("text input needs a g2p(text, language) callable (G2P is outside this engine)")
@@ -281,7 +282,7 @@ class GENIE:
                    text_bert: Optional[np.ndarray] = None, g2p: Optional[Callable] = None,
                    sampler: Optional[Sampler] = None, vocoder_cus: int = 64, speed: float = 1.0,
                    sample_rate: Optional[int] = None, pcm16: bool = False, loudness: Optional[float] = None,
-                   peak: Optional[float] = None):
+                   peak: Optional[float] = None, pause: Optional[float] = None, trim: Optional[float] = None):
         """tts over a list of sentences, yielding each sentence's audio in order (the
         reference runs them one after the other: TTSPlayer._tts_worker_loop,
         Core/TTSPlayer.py:56-107).  Engine-backed sessions pipeline them: sentence i's
@@ -290,8 +291,10 @@ class GENIE:
         those CUs during sentence i's decode (gsv_t2s_prefetch), so sentence i is
         yielded once sentence i+1's T2S is done.  Same tokens and audio as calling
         tts per sentence.  speed, sample_rate / pcm16, loudness / peak: as for tts, of every
-        sentence on its own; the output stage and the measurement run on the vocoder's CUs too."""
-        opts = vocoder_options(speed, sample_rate, pcm16, loudness, peak)   # a bad value fails before anything starts
+        sentence on its own; the output stage and the measurement run on the vocoder's CUs too.
+        pause / trim: every sentence, the last included, is cut to its speech and followed by its
+        pause on the GPU; the yielded array has the joined length."""
+        opts = vocoder_options(speed, sample_rate, pcm16, loudness, peak, pause, trim)   # a bad value fails before anything starts
         speed = opts.pop("speed", 1.0)
         eng = _engine_of(encoder, first_stage_decoder, stage_decoder, vocoder)
         if eng is None or vocoder_cus <= 0 or len(texts) < 2:
@@ -342,7 +345,7 @@ class GENIE:
                     break
                 if pending is not None:
                     eng.vits_wait()
-                    done, pending = pending, None
+                    done, pending = eng.vits_joined([pending])[0], None
                     yield done.cpu().numpy()
                 G = sem.size
                 eps = vocoder.eps(G, speed)
@@ -356,7 +359,7 @@ class GENIE:
                 pending = eng.vits_decode_async(item, vocoder.noise_scale)
             if pending is not None:
                 eng.vits_wait()
-                done, pending = pending, None
+                done, pending = eng.vits_joined([pending])[0], None
                 yield done.cpu().numpy()
         finally:   # stopped, failed or abandoned: started generates and the vocoder call complete
             while getattr(eng, "_gq", None):
@@ -401,19 +404,19 @@ class GENIE:
     def tts_batch(self, items: Sequence[tuple], prompt_audio: ReferenceAudio, model, sampler: Sampler,
                   speed: Union[float, Sequence[float]] = 1.0, samplers: Optional[Sequence[Sampler]] = None,
                   streams: Optional[Sequence[int]] = None, sample_rate=None, pcm16=False, loudness=None,
-                  peak=None) -> List[np.ndarray]:
+                  peak=None, pause=None, trim=None) -> List[np.ndarray]:
         """Batched synthesis for one character and reference: items are
         (text_seq, text_bert|None[, force_steps]).  All sequences decode together
         (one multi-sequence persistent launch, ragged: a finished sequence drops out);
         the vocoder runs each utterance's text/flow part on concurrent lanes and the
         generator once over the whole batch (gsv_vits_decode_batch).  samplers / streams: one
         sampler (and Philox stream) per item instead of `sampler`, still one launch
-        (Engine.t2s_generate).  speed, sample_rate / pcm16, loudness / peak: one value for all
-        items or one per item (tts_batch_vocoder)."""
+        (Engine.t2s_generate).  speed, sample_rate / pcm16, loudness / peak, pause / trim: one
+        value for all items or one per item (tts_batch_vocoder)."""
         toks = (self.tts_batch_t2s(items, prompt_audio, model, sampler) if samplers is None and streams is None
                 else self.tts_batch_t2s(items, prompt_audio, model, sampler, samplers=samplers, streams=streams))
         wavs = self.tts_batch_vocoder(items, toks, prompt_audio, model, speed=speed, sample_rate=sample_rate,
-                                      pcm16=pcm16, loudness=loudness, peak=peak)
+                                      pcm16=pcm16, loudness=loudness, peak=peak, pause=pause, trim=trim)
         return [w if isinstance(w, np.ndarray) else w.cpu().numpy() for w in wavs]
 
     def tts_batch_t2s(self, items: Sequence[tuple], prompt_audio: ReferenceAudio, model, sampler: Sampler,
@@ -432,16 +435,18 @@ class GENIE:
 
     def tts_batch_vocoder(self, items: Sequence[tuple], toks, prompt_audio: ReferenceAudio, model,
                           overlapped: bool = False, speed: Union[float, Sequence[float]] = 1.0,
-                          sample_rate=None, pcm16=False, loudness=None, peak=None):
+                          sample_rate=None, pcm16=False, loudness=None, peak=None, pause=None, trim=None):
         """The vocoder half of tts_batch.  overlapped=True (engine-backed vocoder only) starts
         the batch on the vocoder lanes and returns device tensors that are valid after
         model.ENGINE.vits_batch_wait(); the T2S of the next batch runs beside it
         (gsv_vits_decode_batch_async).  speed, sample_rate / pcm16, loudness / peak
         (engine.vocoder_options): one value or one per item (None entries: that item as ever).  A
         batch may mix them: one launch of the engine's output stage converts the whole batch, and
-        the items with a target are measured in one pass and their gains applied by that launch."""
+        the items with a target are measured in one pass and their gains applied by that launch.
+        pause / trim: the same way; overlapped, the tensors hold the longest a sentence can get and
+        model.ENGINE.vits_joined(them) cuts them to their joined lengths after the wait."""
         eng = model.ENGINE
-        opts = vocoder_options_each(len(items), speed, sample_rate, pcm16, loudness, peak)   # before any GPU work
+        opts = vocoder_options_each(len(items), speed, sample_rate, pcm16, loudness, peak, pause, trim)   # before any GPU work
         cond = _cond(prompt_audio, model.VITS, model.PROMPT_ENCODER, eng)   # the reference branch once per reference
         if getattr(model.VITS, "engine", None) is not eng:
             return [model.VITS.run(None, {"text_seq": it[0], "pred_semantic": tok.reshape(1, 1, -1), **cond, **o})[0]

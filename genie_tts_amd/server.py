@@ -13,7 +13,10 @@ CPU ONNX session set, and uvicorn `workers > 1` cannot share its globals).
                                           with `sample_rate` in the payload the chunks are the
                                           GPU's int16 samples at that rate (X-Sample-Rate);
                                           with `loudness` (LUFS) / `peak` each sentence is
-                                          normalised on the GPU first (X-Loudness)
+                                          normalised on the GPU first (X-Loudness);
+                                          with `pause` (seconds) / `trim` (dBFS) each
+                                          sentence is cut to its speech and followed by its
+                                          pause on the GPU
   POST /stop                          -> every worker
 
 A worker is a spawned process with HIP_VISIBLE_DEVICES set before anything touches
@@ -123,7 +126,8 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
         for prefix, check in (("speed", lambda: vocoder_options(speed=msg.get("speed"))),
                               ("sampling", lambda: check_sampling(**{k: msg.get(k) for k in SAMPLING_FIELDS})),
                               ("sample_rate", lambda: vocoder_options(sample_rate=msg.get("sample_rate"))),
-                              ("loudness", lambda: vocoder_options(loudness=msg.get("loudness"), peak=msg.get("peak")))):
+                              ("loudness", lambda: vocoder_options(loudness=msg.get("loudness"), peak=msg.get("peak"))),
+                              ("join", lambda: vocoder_options(pause=msg.get("pause"), trim=msg.get("trim")))):
             try:
                 got[prefix] = check()
             except (TypeError, ValueError) as e:
@@ -133,7 +137,7 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
         r = {"id": msg["id"], "character_name": msg["character_name"], "sentences": sents, "next": 0,
              "force_steps": int(msg.get("force_steps") or 0), "save_path": msg.get("save_path"),
              "chunks": [], "speed": got["speed"].get("speed", 1.0), "sampling": got["sampling"], "sampler": None,
-             "sample_rate": got["sample_rate"].get("sample_rate"), **got["loudness"]}
+             "sample_rate": got["sample_rate"].get("sample_rate"), **got["loudness"], **got["join"]}
         resolve_sampler(r, model_manager.get(r["character_name"]))
         pending.append(r)
 
@@ -155,6 +159,7 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
         try:
             if eng is not None:
                 eng.vits_batch_wait()
+                wavs = eng.vits_joined(wavs)      # (a request with `trim`: its sentence's joined length)
             wavs = [w if isinstance(w, np.ndarray) else w.cpu().numpy() for w in wavs]
         except Exception as e:       # noqa: BLE001
             for r in group:
@@ -247,6 +252,8 @@ def _worker_main(index: int, conn, cfg: dict) -> None:
                 rate.update(sample_rate=out_rates, pcm16=[v is not None for v in out_rates])
             if any("loudness" in r for r in group):     # ... and requests with and without a loudness target
                 rate.update(loudness=[r.get("loudness") for r in group], peak=[r.get("peak") for r in group])
+            if any("pause" in r or "trim" in r for r in group):   # ... and with and without a pause or a trim
+                rate.update(pause=[r.get("pause") for r in group], trim=[r.get("trim") for r in group])
             wavs = tts_client.tts_batch_vocoder(items, toks, ref, m, overlapped=overlapped, **rate)
         except Exception as e:       # noqa: BLE001
             finish_inflight()
@@ -502,6 +509,11 @@ def create_app(router: Router):
         # Header X-Loudness; absent: the level the voice has, as ever
         loudness: Optional[float] = None
         peak: Optional[float] = None
+        # the sentence join on the GPU: seconds of silence behind every sentence (0 .. 5, GPT-SoVITS's
+        # fragment_interval) and the threshold in dBFS (-80 .. -20) under which a sentence's leading
+        # and trailing audio is cut; a value out of range is a 400.  Absent: butt-joined, as ever
+        pause: Optional[float] = None
+        trim: Optional[float] = None
 
     def check(res: List[dict]) -> None:
         bad = [r for r in res if r["kind"] == "error"]
@@ -545,6 +557,10 @@ def create_app(router: Router):
             vocoder_options(loudness=payload.loudness, peak=payload.peak)
         except ValueError as e:
             raise HTTPException(status_code=400, detail=f"loudness: {e}")
+        try:
+            vocoder_options(pause=payload.pause, trim=payload.trim)
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=f"join: {e}")
         gen = router.tts(character_name=payload.character_name, text=payload.text,
                          split_sentence=payload.split_sentence, save_path=payload.save_path,
                          force_steps=payload.force_steps, speed=payload.speed,
@@ -552,7 +568,8 @@ def create_app(router: Router):
                                               ("temperature", payload.temperature),
                                               ("repetition_penalty", payload.repetition_penalty),
                                               ("seed", payload.seed), ("sample_rate", payload.sample_rate),
-                                              ("loudness", payload.loudness), ("peak", payload.peak))
+                                              ("loudness", payload.loudness), ("peak", payload.peak),
+                                              ("pause", payload.pause), ("trim", payload.trim))
                             if v is not None})
         try:    # surface "not found" as 404 before the stream starts, as the reference does
             first = await gen.__anext__()
@@ -560,7 +577,7 @@ def create_app(router: Router):
             first = None
         except RuntimeError as e:
             code = (404 if "not found" in str(e) else
-                    400 if str(e).startswith(("speed:", "sampling:", "sample_rate:", "loudness:")) else 500)
+                    400 if str(e).startswith(("speed:", "sampling:", "sample_rate:", "loudness:", "join:")) else 500)
             raise HTTPException(status_code=code, detail=str(e))
 
         async def body():

@@ -174,7 +174,7 @@ class VitsSession(_Session):
     Philox N(0,1) stream, a fresh seed per call; noise="zero" is the deterministic
     test mode; `eps_fn(G) -> [192, 2G]` fixes it explicitly.
 
-    Optional feed entries "speed", "sample_rate", "pcm16", "loudness" and "peak": the call's
+    Optional feed entries "speed", "sample_rate", "pcm16", "loudness", "peak", "pause" and "trim": the call's
     engine.vocoder_options (the graph was exported with speed fixed at 1 and has no output stage).
     At a speed the latent is resampled to T' frames before enc_p.proj, and eps_fn is called as
     `eps_fn(G, T') -> [192, T']`.  A V2 feed may carry "ge" [512] in place of "ref_audio": the

@@ -395,6 +395,67 @@ int gsv_audio_normalize(gsv_engine* eng, const float* audio_32k, int32_t n_in, f
  * can be tested apart from the gate. */
 int gsv_debug_loudness_hops(gsv_engine* eng, const float* audio, int32_t n, float* e, void* stream);
 
+/* Sentence join: the pause behind a sentence and the trim of its edge silence (GPT-SoVITS appends
+ * `fragment_interval` seconds of zeros to every fragment; the sentences of a stream are otherwise
+ * butt-joined, each with the uneven lead-in its vocoder pass produced).  The engine finds where an
+ * item's speech begins and ends on the GPU, and the output stage converts only that span and
+ * appends the pause: no host round trip lies between the measurement and the conversion.
+ *   Frames: the item's final 32 kHz float32 audio x[0..n) is cut into frames of 320 samples
+ *   (10 ms); the last may be partial, with c samples (else c = 320).  Frame f is active when
+ *   sum x[i]^2 > T * c, the squares and the sum taken in double (a float32 squared is exact in
+ *   double), T = 10^(trim / 10) computed once on the host in double from the float32 trim widened
+ *   to double.
+ *   Span: f0 and f1 the first and last active frames; begin = max(0, 320 f0 - 640),
+ *   end = min(n, 320 (f1 + 1) + 640): a guard of GSV_JOIN_GUARD = 640 samples (20 ms) on either
+ *   side.  No active frame, or n == 0: begin = end = 0, and the sentence is its pause alone.
+ *   Without a trim the span is [0, n).
+ *   Output: n_speech = gsv_audio_samples(end - begin, out_rate);
+ *   pause_n = gsv_join_pause_samples(out_rate, pause) = (int)((double)out_rate * (double)pause), the
+ *   float32 pause widened to double (out_rate 0 is 32000): callers take it from that function and
+ *   never recompute it.  out[0 .. n_speech) is exactly what gsv_audio_convert gives for
+ *   audio[begin .. end) alone -- the same fma chain, samples outside the span counting as zeros and
+ *   never read as filter context; out[n_speech .. n_speech + pause_n) is zeros (+0.0f or int16 0);
+ *   nothing beyond is written.  `out` must hold gsv_join_samples(n, out_rate, pause) =
+ *   gsv_audio_samples(n, out_rate) + pause_n samples.
+ *   Loudness: with a target, the measurement, the peak and the gain stay those of the whole
+ *   untrimmed item (the gates already ignore silence); the gain multiplies the span's samples.
+ *   `audio` (32 kHz float32) is still written, untrimmed and bit-unchanged.
+ *   Span record: device int32[4] {begin, end, n_speech, n_out = n_speech + pause_n}, written on
+ *   the device.  The same bits whatever the launch: alone, in a batch, on the vocoder's stream.
+ * gsv_join rides beside an item as gsv_loudness does and carries its fields (target 0: no
+ * loudness) plus trim: threshold in dBFS, 0 == off, valid -80 .. -20; pause: seconds, 0 == none,
+ * valid 0 .. 5; span: device int32[4] or NULL.  Out of range is GSV_E_ARG before any launch.  An
+ * item with a trim, a pause or a span needs `out`; a trim needs n <= 640 * 4096.  An item whose
+ * gsv_join is all zero is the call without it: the same launches, the same bits. */
+#define GSV_JOIN_FRAME 320
+#define GSV_JOIN_GUARD 640
+typedef struct { float target; float peak; float* stats; float trim; float pause; int32_t* span; } gsv_join;
+/* Samples of `pause` seconds at out_rate, and the bound of `out` (see above); GSV_E_ARG for an
+ * unsupported rate, a negative n_in or a pause outside 0 .. 5.  Pure: need no device. */
+int gsv_join_pause_samples(int32_t out_rate, float pause);
+int gsv_join_samples(int32_t n_in, int32_t out_rate, float pause);
+/* The `_join` twins of the entries that take items: join is [n] (one per item; NULL: the plain
+ * call).  The plain and the `_norm` entries forward here: one body, one set of checks.  A batch is
+ * one frame pass and one span pass plus the stage launch per 256 items; after an fp16-range re-run
+ * the re-run's audio is measured; under gsv_vits_decode_async_join all run on the vocoder's
+ * stream.  join is copied: it need not outlive the call (the stats and span buffers must, until
+ * the wait). */
+int gsv_vits_decode_item_join(gsv_engine* eng, const gsv_vits_item* item, const gsv_join* join,
+                              float noise_scale, void* stream);
+int gsv_vits_decode_batch_join(gsv_engine* eng, int32_t n, const gsv_vits_item* items, const gsv_join* join,
+                               float noise_scale, void* stream);
+int gsv_vits_decode_batch_async_join(gsv_engine* eng, int32_t n, const gsv_vits_item* items,
+                                     const gsv_join* join, float noise_scale, void* stream);
+int gsv_vits_decode_async_join(gsv_engine* eng, const gsv_vits_item* item, const gsv_join* join,
+                               float noise_scale, void* stream);
+/* The stage alone: gsv_audio_convert (gsv_audio_normalize with a target) of the span of audio_32k
+ * plus the pause; out holds gsv_join_samples(n_in, out_rate, join->pause).  join NULL: gsv_audio_convert. */
+int gsv_audio_join(gsv_engine* eng, const float* audio_32k, int32_t n_in, const gsv_join* join,
+                   int32_t out_rate, int32_t out_format, void* out, void* stream);
+/* Debug: the frames' sums of squares (device double [ceil(n / 320)]) of audio (device f32 [n],
+ * n <= 640 * 4096) alone, so the frame pass can be tested apart from the span logic. */
+int gsv_debug_join_frames(gsv_engine* eng, const float* audio, int32_t n, double* sums, void* stream);
+
 /* The T2S side of the same pipeline: encode + prefill the NEXT sentence ahead, on
  * the vocoder CUs while the current sentence decodes (the reference's per-sentence
  * encoder + first-stage decoder, Inference.py:63-72, moved off the critical path).
