@@ -174,12 +174,13 @@ int gsv_engine::audio_item(const gsv_vits_item& u, AudioOutItem* a) const {
 // the item table this call site owns (AO_SYNC: the engine stream's synchronous calls, AO_ASYNC:
 // the overlapped vocoder call, AO_BATCH_AT: a batch): a region is refilled only after the launch
 // that last read it has finished, which it has in practice (the wait is for the previous call's
-// stage, and a vocoder pass lies between two of them).  norm (null: none) lies beside items: the
+// stage, and a vocoder pass lies between two of them).  spec (null: none) lies beside items: the
 // entries with a target are measured first, one pass per launch (loudness.hip), and their
 // conversions read the gain from the measurement's slot on the device.  The entries with a trim,
 // a pause or a span record go through the join stage the same way (join.hip): their conversions
 // read the span from the slot's record, and n_out of their table entry is the host's upper bound.
-int gsv_engine::audio_out(const AudioOutItem* items, const gsv_join* norm, int n, int region, hipStream_t s) {
+// An all-zero entry is the same as none: no measurement, no launch, the table entry as it is.
+int gsv_engine::audio_out(const AudioOutItem* items, const gsv_join* spec, int n, int region, hipStream_t s) {
     if (!ao_tab) return set_error(GSV_E_STATE, "output stage not initialised");
     const int base = region, cap = region == AO_BATCH_AT ? AO_BATCH : 1;   // (a region is its first slot)
     hipEvent_t ev = ao_ev[region];
@@ -192,9 +193,9 @@ int gsv_engine::audio_out(const AudioOutItem* items, const gsv_join* norm, int n
         std::vector<JoinItem> join;
         for (int j = 0; j < m; ++j) {
             ao_pin[base + j] = items[i + j];
-            if (norm && join_active(norm[i + j])) {
+            if (spec && join_active(spec[i + j])) {
                 // its span goes into slot base + j's record, which this item's conversion reads on the device
-                const gsv_join& l = norm[i + j];
+                const gsv_join& l = spec[i + j];
                 const AudioOutItem& a = items[i + j];
                 const int pause_n = join_pause_samples(RATES[a.rate], l.pause);
                 if (pause_n < 0) return set_error(GSV_E_ARG, "pause: 0 .. 5 seconds");
@@ -206,9 +207,9 @@ int gsv_engine::audio_out(const AudioOutItem* items, const gsv_join* norm, int n
                 ao_pin[base + j].n_out += pause_n;
             }
             max_out = std::max(max_out, ao_pin[base + j].n_out);
-            if (!norm || norm[i + j].target == 0.f) continue;
+            if (!spec || spec[i + j].target == 0.f) continue;
             // measured into slot base + j, whose gain this item's conversion reads on the device
-            const gsv_join& l = norm[i + j];
+            const gsv_join& l = spec[i + j];
             loud.resize(m, LoudItem{nullptr, nullptr, -1, 0.f, 1.f, 0});
             loud[j] = LoudItem{items[i + j].src, l.stats, items[i + j].n_in, l.target,
                                l.peak == 0.f ? 0.8912509381337456f : l.peak, 0};
@@ -226,16 +227,16 @@ int gsv_engine::audio_out(const AudioOutItem* items, const gsv_join* norm, int n
 }
 
 // The items of a vocoder call that carry `out`, converted from their final `audio`.
-int gsv_engine::audio_out_items(const gsv_vits_item* it, const gsv_join* norm, int n, int region, hipStream_t s) {
+int gsv_engine::audio_out_items(const gsv_vits_item* it, const gsv_join* spec, int n, int region, hipStream_t s) {
     std::vector<AudioOutItem> a;
     std::vector<gsv_join> l;
     for (int i = 0; i < n; ++i) {
         if (!it[i].out) continue;
         a.emplace_back();
         if (audio_item(it[i], &a.back())) return set_error(GSV_E_ARG, "bad output rate or format");
-        if (norm) l.push_back(norm[i]);
+        if (spec) l.push_back(spec[i]);
     }
-    return a.empty() ? 0 : audio_out(a.data(), norm ? l.data() : nullptr, (int)a.size(), region, s);
+    return a.empty() ? 0 : audio_out(a.data(), spec ? l.data() : nullptr, (int)a.size(), region, s);
 }
 
 extern "C" int gsv_audio_samples(int32_t n_in, int32_t out_rate) {
@@ -243,27 +244,34 @@ extern "C" int gsv_audio_samples(int32_t n_in, int32_t out_rate) {
     return n < 0 || n > INT32_MAX ? GSV_E_ARG : (int)n;
 }
 
-// The output stage alone on one buffer, its arguments checked first; l: null, or the target to bring it
-// to (needed when `target`) and the join spec.
-static int audio_entry(gsv_engine* eng, const float* audio_32k, int32_t n_in, const gsv_join* l, bool target,
+int gsv::check_spec(const gsv_join& spec, bool has_out, int n_in) {
+    if (int r = check_loudness(gsv_loudness{spec.target, spec.peak, spec.stats})) return r;
+    if (spec.target != 0.f && !has_out) return set_error(GSV_E_ARG, "loudness target on an item without `out`");
+    if (spec.target != 0.f && n_in > LD_MAX_N) return set_error(GSV_E_ARG, "loudness: more than 640 * 4096 samples");
+    if (int r = check_join(spec)) return r;
+    if (join_active(spec) && !has_out) return set_error(GSV_E_ARG, "pause or trim on an item without `out`");
+    if (spec.trim != 0.f && n_in > JN_MAX_N) return set_error(GSV_E_ARG, "trim: more than 640 * 4096 samples");
+    return 0;
+}
+
+// The output stage alone on one buffer, its arguments checked first; spec: null, or the target to bring
+// it to (needed when `target`) and the join options.  (A missing `out` is reported below as a null buffer.)
+static int audio_entry(gsv_engine* eng, const float* audio_32k, int32_t n_in, const gsv_join* spec, bool target,
                        int32_t out_rate, int32_t out_format, void* out, void* stream) {
     if (!eng) return set_error(GSV_E_ARG, "null engine");
     const int rate = audio_rate_index(out_rate), n_out = gsv_audio_samples(n_in, out_rate);
     if (rate < 0 || n_out < 0) return set_error(GSV_E_ARG, "out_rate: 8000, 16000, 22050, 24000, 32000, 44100 or 48000");
     if (out_format < 0 || out_format > 1) return set_error(GSV_E_ARG, "out_format: 0 (float32) or 1 (int16)");
-    if (l) {
-        if (target && l->target == 0.f) return set_error(GSV_E_ARG, "loudness target: -50 .. -5 LUFS");
-        if (int r = check_loudness(gsv_loudness{l->target, l->peak, l->stats})) return r;
-        if (l->target != 0.f && n_in > LD_MAX_N) return set_error(GSV_E_ARG, "loudness: more than 640 * 4096 samples");
-        if (int r = check_join(*l)) return r;
-        if (l->trim != 0.f && n_in > JN_MAX_N) return set_error(GSV_E_ARG, "trim: more than 640 * 4096 samples");
+    if (spec) {
+        if (target && spec->target == 0.f) return set_error(GSV_E_ARG, "loudness target: -50 .. -5 LUFS");
+        if (int r = check_spec(*spec, true, n_in)) return r;
     }
     if (n_in > 0 && (!audio_32k || !out)) return set_error(GSV_E_ARG, "null audio buffer");
-    if (l && l->pause != 0.f && !out) return set_error(GSV_E_ARG, "null audio buffer");
+    if (spec && spec->pause != 0.f && !out) return set_error(GSV_E_ARG, "null audio buffer");
     hipSetDevice(eng->device);
     StreamScope sc(eng, stream);
     const AudioOutItem a{audio_32k, out, n_in, n_out, rate, out_format, nullptr};
-    return eng->audio_out(&a, l, 1, gsv_engine::AO_SYNC, sc.st());
+    return eng->audio_out(&a, spec, 1, gsv_engine::AO_SYNC, sc.st());
 }
 
 extern "C" int gsv_audio_convert(gsv_engine* eng, const float* audio_32k, int32_t n_in, int32_t out_rate,
@@ -273,8 +281,8 @@ extern "C" int gsv_audio_convert(gsv_engine* eng, const float* audio_32k, int32_
 
 extern "C" int gsv_audio_normalize(gsv_engine* eng, const float* audio_32k, int32_t n_in, float target, float peak,
                                    int32_t out_rate, int32_t out_format, void* out, float* stats, void* stream) {
-    const gsv_join l{target, peak, stats, 0.f, 0.f, nullptr};
-    return audio_entry(eng, audio_32k, n_in, &l, true, out_rate, out_format, out, stream);
+    const gsv_join spec{target, peak, stats, 0.f, 0.f, nullptr};
+    return audio_entry(eng, audio_32k, n_in, &spec, true, out_rate, out_format, out, stream);
 }
 
 extern "C" int gsv_audio_join(gsv_engine* eng, const float* audio_32k, int32_t n_in, const gsv_join* join,

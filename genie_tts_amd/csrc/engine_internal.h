@@ -26,6 +26,9 @@ int set_error(int code, const std::string& msg);
 int check_loudness(const gsv_loudness& l);   // target 0 (off) or in [-50, -5], peak 0 or in (0, 1]
 int check_join(const gsv_join& j);           // trim 0 (off) or in [-80, -20], pause in [0, 5]
 bool join_active(const gsv_join& j);         // a trim, a pause or a span record asked for
+// One item's spec before anything runs: both checks above, `out` present where a target, a trim or a
+// pause needs it, and n_in (32 kHz samples) within what the loudness and trim measurements take.
+int check_spec(const gsv_join& spec, bool has_out, int n_in);
 int join_pause_samples(int out_rate, float pause);   // (int)((double)rate * (double)pause); -1: bad rate or pause
 int check_sampler(const gsv_sampler* s);   // top_k in [1, 64], top_p in (0, 1] or 0 (unset)
 inline float norm_top_p(float p) { return p == 0.f ? 1.f : p; }   // gsv_sampler.top_p: 0 means 1
@@ -390,16 +393,11 @@ struct gsv_engine {
     // refill; 0: 4 was 0.2 % faster alone but equal in the pipelined stream (profiles/r06k_headline_ab.txt)
     int persist1_pf_delay = 0;
     int persist1_knob[4] = {0, 0, 0, 0};   // options "knob0".."knob3": single-sequence kernel tuning variants
-    // speed: the item's speech rate (0 == 1: no resample); the pass runs proj, the flows and the
-    // generator at vits_frames(n_sem, speed) frames
-    int vits_decode(const int64_t* text_seq, int n_text, const int64_t* sem, int n_sem,
-                    const float* ref_audio, int n_audio, const float* ge, const float* ge_adv,
-                    const float* eps, uint64_t noise_seed, float noise_scale, float* audio, hipStream_t st,
-                    float speed = 0.f);
-    int vits_decode_pass(gsv::VitsWorkspace& W, const int64_t* text_seq, int n_text, const int64_t* sem, int n_sem,
-                         const float* ref_audio, int n_audio, const float* ge, const float* ge_adv,
-                         const float* eps, uint64_t noise_seed, float noise_scale, float* audio, hipStream_t st,
-                         int* ovf, bool timed, float speed = 0.f);
+    // u: one vocoder item, its inputs, noise source (noise_mode), `audio` and speech rate (speed 0 == 1:
+    // no resample); the pass runs proj, the flows and the generator at vits_frames(n_sem, speed) frames
+    int vits_decode(const gsv_vits_item& u, float noise_scale, hipStream_t st);
+    int vits_decode_pass(gsv::VitsWorkspace& W, const gsv_vits_item& u, float noise_scale, hipStream_t st, int* ovf,
+                         bool timed);
     // A segmented batch's front part in one pass (vits_front with fs): the utterances back to
     // back along the frame axis (the generator's layout) and along the text axis, zero gaps.
     struct FrontSeg {
@@ -417,10 +415,8 @@ struct gsv_engine {
         const float* gem = nullptr;            // [n][512] MRTE vector
         float* gcond = nullptr;                // [n][1536] scratch
     };
-    int vits_front(gsv::VitsWorkspace& W, const int64_t* text_seq, int n_text, const int64_t* sem, int n_sem,
-                   const float* ref_audio, int n_audio, const float* ge, const float* ge_adv, const float* eps,
-                   uint64_t noise_seed, float noise_scale, float* dcond_out, hipStream_t st,
-                   const FrontSeg* fs = nullptr, float speed = 0.f);
+    int vits_front(gsv::VitsWorkspace& W, const gsv_vits_item& u, float noise_scale, float* dcond_out, hipStream_t st,
+                   const FrontSeg* fs = nullptr);   // (u is unused with fs)
     int seg_front(hipStream_t st);
     int seg_front_tables(hipStream_t s);   // FrontSeg of vb_items into sgb (host build, one copy)            // the packed front of vb_items (vb_packed) into sgb.z / sgb.dcond
     // segmented vocoder batch (option "seg_vocoder", default 1): every utterance's front part
@@ -471,7 +467,7 @@ struct gsv_engine {
     int* vflags = nullptr;
     int* vflags_host = nullptr;
     int vflag_cap = 0;
-    int vits_decode_batch(int n, const gsv_vits_item* it, const gsv_join* norm, float noise_scale, hipStream_t s);
+    int vits_decode_batch(int n, const gsv_vits_item* it, const gsv_join* spec, float noise_scale, hipStream_t s);
     // overlapped batch (gsv_vits_decode_batch_async): issued by lane threads that may still
     // run when the call returns; vits_batch_finish joins
     std::vector<gsv_vits_item> vb_items;
@@ -515,7 +511,7 @@ struct gsv_engine {
     gsv_vits_item vcall{};
     float vcall_scale = 0.f;
     int set_vocoder_cus(int K);
-    int vits_async(const gsv_vits_item& u, const gsv_join* norm, float noise_scale, hipStream_t caller);
+    int vits_async(const gsv_vits_item& u, const gsv_join* spec, float noise_scale, hipStream_t caller);
     int vits_wait(hipStream_t caller);
     int vits_launch_queued(hipStream_t s = nullptr);
     hipStream_t vlast = nullptr;       // stream the pending vocoder call was launched on
@@ -561,9 +557,9 @@ struct gsv_engine {
     hipEvent_t ao_ev[3] = {};
     int audio_out_init();
     int audio_item(const gsv_vits_item& u, gsv::AudioOutItem* a) const;   // GSV_E_ARG: bad rate / format / speed
-    // norm (null: none): [n] beside items; an entry with a target is measured first and its gain applied
-    int audio_out(const gsv::AudioOutItem* items, const gsv_join* norm, int n, int region, hipStream_t s);
-    int audio_out_items(const gsv_vits_item* it, const gsv_join* norm, int n, int region, hipStream_t s);
+    // spec (null: none): [n] beside items; an entry with a target is measured first and its gain applied
+    int audio_out(const gsv::AudioOutItem* items, const gsv_join* spec, int n, int region, hipStream_t s);
+    int audio_out_items(const gsv_vits_item* it, const gsv_join* spec, int n, int region, hipStream_t s);
     // ---- loudness stage (loudness.hip): one workspace slot per slot of the output stage's item table
     gsv::LoudFilter lo_filter{};
     gsv::LoudWorkspace lo_ws{};
@@ -572,8 +568,8 @@ struct gsv_engine {
     hipEvent_t lo_ev[3] = {};
     int loudness_init();
     int loudness_measure(const gsv::LoudItem* items, int m, int region, hipStream_t s);
-    gsv_join vcall_norm{};                 // of the overlapped vocoder call (all zero: none)
-    std::vector<gsv_join> vb_norm;         // of the running batch (empty: none)
+    gsv_join vcall_spec{};                 // of the overlapped vocoder call (all zero: none)
+    std::vector<gsv_join> vb_spec;         // of the running batch (empty: none)
     // ---- join stage (join.hip): edge-silence trim and pause; slots, regions and events as above
     gsv::JoinWorkspace jn_ws{};
     gsv::JoinItem* jn_tab = nullptr;   // [AO_SLOTS] device item table

@@ -518,10 +518,7 @@ static int ensure_vits_ws(gsv_engine* e, VitsWorkspace& W, int T, int S, int n_a
 // large for fp16 sets the overflow flag, and the utterance is then decoded again
 // on the f32 path (same kernels otherwise), so the output never depends on the
 // fp16 range.  The flag check is a host sync on the caller's stream.
-int gsv_engine::vits_decode(const int64_t* text_seq, int n_text, const int64_t* sem, int G,
-                            const float* ref_audio, int n_audio, const float* ge_in,
-                            const float* ge_adv_in, const float* eps, uint64_t noise_seed, float noise_scale,
-                            float* audio, hipStream_t s, float speed) {
+int gsv_engine::vits_decode(const gsv_vits_item& u, float noise_scale, hipStream_t s) {
     if (use_convh && !vovf) {   // stream-ordered zeroing: no null-stream call beside running lanes / captures
         if (hipMalloc(&vovf, 64) != hipSuccess || hipHostMalloc((void**)&vovf_host, 64, hipHostMallocDefault) != hipSuccess)
             return set_error(GSV_E_HIP, "overflow flag alloc");
@@ -532,22 +529,16 @@ int gsv_engine::vits_decode(const int64_t* text_seq, int n_text, const int64_t* 
     if (vb_active)
         if (int r = vits_batch_finish(nullptr)) return r;
     if (!use_convh) {
-        if (int r = vits_decode_pass(vws, text_seq, n_text, sem, G, ref_audio, n_audio, ge_in, ge_adv_in, eps,
-                                     noise_seed, noise_scale, audio, s, nullptr, timing, speed))
-            return r;
+        if (int r = vits_decode_pass(vws, u, noise_scale, s, nullptr, timing)) return r;
         return vits_read_ms();
     }
-    if (int r = vits_decode_pass(vws, text_seq, n_text, sem, G, ref_audio, n_audio, ge_in, ge_adv_in, eps, noise_seed,
-                                 noise_scale, audio, s, vovf, timing, speed))
-        return r;
+    if (int r = vits_decode_pass(vws, u, noise_scale, s, vovf, timing)) return r;
     hipMemcpyAsync(vovf_host, vovf, 4, hipMemcpyDeviceToHost, s);
     if (hipStreamSynchronize(s) != hipSuccess) return set_error(GSV_E_HIP, "vits sync");
     if (*vovf_host == 0) return vits_read_ms();
     hipMemsetAsync(vovf, 0, 4, s);
     ++vits_f32_reruns;
-    if (int r = vits_decode_pass(vws, text_seq, n_text, sem, G, ref_audio, n_audio, ge_in, ge_adv_in, eps, noise_seed,
-                                 noise_scale, audio, s, nullptr, timing, speed))
-        return r;
+    if (int r = vits_decode_pass(vws, u, noise_scale, s, nullptr, timing)) return r;
     return vits_read_ms();
 }
 
@@ -718,7 +709,7 @@ int gsv_engine::set_vocoder_cus(int K) {
 // The call is queued, not launched: its ~400 launches are issued by the next
 // T2S generate right after the persistent decode kernel (vits_launch_queued), so
 // the host enqueues them while the GPU decodes instead of delaying that T2S.
-int gsv_engine::vits_async(const gsv_vits_item& u, const gsv_join* norm, float noise_scale, hipStream_t caller) {
+int gsv_engine::vits_async(const gsv_vits_item& u, const gsv_join* spec, float noise_scale, hipStream_t caller) {
     if (!vstream) return set_error(GSV_E_STATE, "overlapped vocoder: set option vocoder_cus first");
     if (int r = vits_wait(nullptr)) return r;
     if (vb_active)
@@ -730,7 +721,7 @@ int gsv_engine::vits_async(const gsv_vits_item& u, const gsv_join* norm, float n
     }
     hipEventRecord(vev_in, caller);   // the inputs are ready in the caller's stream order here
     vcall = u;
-    vcall_norm = norm ? *norm : gsv_join{};
+    vcall_spec = spec ? *spec : gsv_join{};
     vcall_scale = noise_scale;
     vqueued = true;
     return 0;
@@ -744,12 +735,9 @@ int gsv_engine::vits_launch_queued(hipStream_t s) {
     if (!s) s = vstream;
     const gsv_vits_item& u = vcall;
     hipStreamWaitEvent(s, vev_in, 0);
-    if (int r = vits_decode_pass(vws, u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge, u.ge_adv,
-                                 u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0,
-                                 vcall_scale, u.audio, s, use_convh ? vovf : nullptr, timing, u.speed))
-        return r;
-    // on the vocoder's stream, behind its pass
-    if (int r = audio_out_items(&u, vcall_norm.target != 0.f || join_active(vcall_norm) ? &vcall_norm : nullptr, 1, AO_ASYNC, s)) return r;
+    if (int r = vits_decode_pass(vws, u, vcall_scale, s, use_convh ? vovf : nullptr, timing)) return r;
+    // on the vocoder's stream, behind its pass (an all-zero spec adds nothing to the stage)
+    if (int r = audio_out_items(&u, &vcall_spec, 1, AO_ASYNC, s)) return r;
     if (use_convh) hipMemcpyAsync(vovf_host, vovf, 4, hipMemcpyDeviceToHost, s);
     hipEventRecord(vev_done, s);
     vpending = true;
@@ -768,13 +756,9 @@ int gsv_engine::vits_wait(hipStream_t caller) {
         const gsv_vits_item& u = vcall;
         hipMemsetAsync(vovf, 0, 4, vlast);
         ++vits_f32_reruns;
-        if (int r = vits_decode_pass(vws, u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge,
-                                     u.ge_adv, u.noise_mode == 1 ? u.eps : nullptr,
-                                     u.noise_mode == 2 ? u.noise_seed : 0, vcall_scale, u.audio, vlast, nullptr,
-                                     timing, u.speed))
-            return r;
+        if (int r = vits_decode_pass(vws, u, vcall_scale, vlast, nullptr, timing)) return r;
         // `out` (and its loudness) from the re-run's audio
-        if (int r = audio_out_items(&u, vcall_norm.target != 0.f || join_active(vcall_norm) ? &vcall_norm : nullptr, 1, AO_ASYNC, vlast)) return r;
+        if (int r = audio_out_items(&u, &vcall_spec, 1, AO_ASYNC, vlast)) return r;
         hipEventRecord(vev_done, vlast);
         if (hipEventSynchronize(vev_done) != hipSuccess) return set_error(GSV_E_HIP, "overlapped vocoder re-run");
     }
@@ -956,28 +940,24 @@ static void vits_generator(const VitsWeights& V, float* const (&gb)[5], const fl
 }
 
 // One utterance on stream s with workspace W.  ovf != NULL: the MRF convs run on
-// the f16-split path and OR 1 into *ovf on an fp16-range overflow.  noise: eps
-// (device [192, T']) if given, else Philox N(0,1) keyed by noise_seed when it is
-// non-zero, else zeros.  timed: phase events (ms[3]) around the pass.  speed: the speech
+// the f16-split path and OR 1 into *ovf on an fp16-range overflow.  The noise of z_p is
+// the item's (vits_front).  timed: phase events (ms[3]) around the pass.  u.speed: the speech
 // rate; T' = vits_frames(G, speed) frames from proj on (2G at speed 0 or 1).
-int gsv_engine::vits_decode_pass(VitsWorkspace& W, const int64_t* text_seq, int n_text, const int64_t* sem, int G,
-                                 const float* ref_audio, int n_audio, const float* ge_in,
-                                 const float* ge_adv_in, const float* eps, uint64_t noise_seed, float noise_scale,
-                                 float* audio, hipStream_t s, int* ovf, bool timed, float speed) {
+int gsv_engine::vits_decode_pass(VitsWorkspace& W, const gsv_vits_item& u, float noise_scale, hipStream_t s, int* ovf,
+                                 bool timed) {
+    const int G = u.n_sem, n_text = u.n_text;
     if (!vits.ready) return set_error(GSV_E_STATE, "VITS weights not loaded");
     if (G <= 0 || n_text <= 0) return set_error(GSV_E_ARG, "empty VITS input");
     if (2 * G > MHA_MAXK_HOST || n_text > MHA_MAXK_HOST) return set_error(GSV_E_CAPACITY, "sequence too long");
-    const int Tp = vits_frames(G, speed);   // the frames after the resample: 2G at speed 1
+    const int Tp = vits_frames(G, u.speed);   // the frames after the resample: 2G at speed 1
     if (Tp < 0) return set_error(GSV_E_ARG, "speed: 0.25 .. 4 (0 or 1: as recorded)");
     if (Tp > VITS_MAXT_OUT) return set_error(GSV_E_CAPACITY, "resampled sequence too long");
-    if (int r = ensure_vits_ws(this, W, 2 * G, n_text, version == GSV_V2PP ? 0 : n_audio, true, Tp)) return r;
+    if (int r = ensure_vits_ws(this, W, 2 * G, n_text, version == GSV_V2PP ? 0 : u.n_audio, true, Tp)) return r;
     SplitkScope sk(W.splitk, W.splitk_cap);
     ConvhScope cs(ovf, convh_tile, convt_f16, mrf_fused, convh_ws == 1 ? stream_cus(s) : 0);
     (void)hipGetLastError();   // the launches below are checked as one batch at the end
     if (timed) hipEventRecord(ev[4], s);
-    if (int r = vits_front(W, text_seq, n_text, sem, G, ref_audio, n_audio, ge_in, ge_adv_in, eps, noise_seed,
-                           noise_scale, W.dcond, s, nullptr, speed))
-        return r;
+    if (int r = vits_front(W, u, noise_scale, W.dcond, s)) return r;
     float* const gb[5] = {W.g0, W.g1, W.g2, W.g3, W.g4};
     // the three resblocks of a stage on three streams (vits_fork, an unmasked engine stream)
     SideStream* sd = vits_fork && ovf && s == stream ? side_of(s) : nullptr;
@@ -996,7 +976,7 @@ int gsv_engine::vits_decode_pass(VitsWorkspace& W, const int64_t* text_seq, int 
             for (float*& p : W.gx) p = nullptr;   // (allocated ones stay in W.owned)
         }
     }
-    vits_generator(vits, gb, W.z, Tp, W.dcond, 0, nullptr, audio, s, sd, sd ? W.gx : nullptr);
+    vits_generator(vits, gb, W.z, Tp, W.dcond, 0, nullptr, u.audio, s, sd, sd ? W.gx : nullptr);
     if (timed) hipEventRecord(ev[5], s);   // read by vits_read_ms once the pass is known to be final
     return hipGetLastError() == hipSuccess ? 0 : set_error(GSV_E_HIP, "vits launch");
 }
@@ -1009,11 +989,16 @@ int gsv_engine::vits_decode_pass(VitsWorkspace& W, const int64_t* text_seq, int 
 // frame axis (fs->Tt columns) and the text axis (fs->St), zero gaps (the convs' seg
 // epilogue, seg-aware LayerNorm / noise / embedding kernels), attention within each
 // utterance (row_seg); ge / ge_m per utterance (vec_sstride); z [192][Tt] in W.z and
-// dcond_out [n][upc].  The per-utterance arguments are unused then.
-int gsv_engine::vits_front(VitsWorkspace& W, const int64_t* text_seq, int n_text, const int64_t* sem, int G,
-                           const float* ref_audio, int n_audio, const float* ge_in, const float* ge_adv_in,
-                           const float* eps, uint64_t noise_seed, float noise_scale, float* dcond_out,
-                           hipStream_t s, const FrontSeg* fs, float speed) {
+// dcond_out [n][upc].  The item u is unused then.
+// The noise of z_p: u.eps (device [192, T']) with noise_mode 1, the Philox N(0,1) stream keyed by
+// u.noise_seed with noise_mode 2 and a non-zero seed, else zeros.
+int gsv_engine::vits_front(VitsWorkspace& W, const gsv_vits_item& u, float noise_scale, float* dcond_out,
+                           hipStream_t s, const FrontSeg* fs) {
+    const int64_t *text_seq = u.text_seq, *sem = u.sem;
+    const int n_text = u.n_text, G = u.n_sem, n_audio = u.n_audio;
+    const float *ref_audio = u.ref_audio, *ge_in = u.ge, *ge_adv_in = u.ge_adv;
+    const float* eps = u.noise_mode == 1 ? u.eps : nullptr;
+    const uint64_t noise_seed = u.noise_mode == 2 ? u.noise_seed : 0;
     const VitsWeights& V = vits;
     if (!V.ready) return set_error(GSV_E_STATE, "VITS weights not loaded");
     const bool pp = version == GSV_V2PP;
@@ -1031,7 +1016,7 @@ int gsv_engine::vits_front(VitsWorkspace& W, const int64_t* text_seq, int n_text
         T = 2 * G;
         S = n_text;
         if (T > MHA_MAXK_HOST || S > MHA_MAXK_HOST) return set_error(GSV_E_CAPACITY, "sequence too long");
-        To = vits_frames(G, speed);
+        To = vits_frames(G, u.speed);
         if (To < 0) return set_error(GSV_E_ARG, "speed: 0.25 .. 4 (0 or 1: as recorded)");
         if (To > VITS_MAXT_OUT) return set_error(GSV_E_CAPACITY, "resampled sequence too long");
         if (int r = ensure_vits_ws(this, W, T, S, pp ? 0 : n_audio, true, To)) return r;
@@ -1167,7 +1152,7 @@ int gsv_engine::vits_front(VitsWorkspace& W, const int64_t* text_seq, int n_text
 // workspace), so up to K vocoder chains -- each a few hundred small launches that
 // under-fill the chip -- overlap on the GPU.  Each utterance has its own overflow
 // flag; after the join, flagged utterances are decoded again on the f32 path.
-int gsv_engine::vits_decode_batch(int n, const gsv_vits_item* it, const gsv_join* norm, float noise_scale,
+int gsv_engine::vits_decode_batch(int n, const gsv_vits_item* it, const gsv_join* spec, float noise_scale,
                                   hipStream_t s) {
     if (n <= 0) return 0;
     if (vb_active)   // an overlapped batch shares the lanes: finish it first
@@ -1175,15 +1160,11 @@ int gsv_engine::vits_decode_batch(int n, const gsv_vits_item* it, const gsv_join
     if (n > 1 && (vpending || vqueued))
         if (int r = vits_wait(nullptr)) return r;
     if (n == 1) {   // one utterance: the engine stream itself, no lane fork/join
-        const gsv_vits_item& u = it[0];
-        if (int r = vits_decode(u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge, u.ge_adv,
-                                u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0,
-                                noise_scale, u.audio, s, u.speed))
-            return r;
-        return audio_out_items(&u, norm, 1, AO_SYNC, s);
+        if (int r = vits_decode(it[0], noise_scale, s)) return r;
+        return audio_out_items(it, spec, 1, AO_SYNC, s);
     }
     vb_items.assign(it, it + n);
-    vb_norm.assign(norm, norm ? norm + n : norm);
+    vb_spec.assign(spec, spec ? spec + n : spec);
     if (int r = vits_batch_launch(noise_scale, s, true)) return r;
     return vits_batch_finish(s);
 }
@@ -1342,9 +1323,7 @@ int gsv_engine::seg_front(hipStream_t st) {
     gather_vecs(B.gem_ptrs, n, vits.mrte_o.cout, B.gem, st);
     if (int r = ensure_vits_ws(this, B.fw, B.T, B.St, 0, false)) return r;
     SplitkScope sk(B.fw.splitk, B.fw.splitk_cap);
-    if (int r = vits_front(B.fw, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, vb_scale, B.dcond,
-                           st, &B.fs))
-        return r;
+    if (int r = vits_front(B.fw, gsv_vits_item{}, vb_scale, B.dcond, st, &B.fs)) return r;
     hipMemcpyAsync(B.z, B.fw.z, (size_t)192 * B.T * 4, hipMemcpyDeviceToDevice, st);
     return 0;
 }
@@ -1499,18 +1478,13 @@ int gsv_engine::vits_batch_launch(float noise_scale, hipStream_t s, bool join) {
                                    sgb.h_len[i]);
                 if (!r) {
                     SplitkScope sk(W.splitk, W.splitk_cap);
-                    r = vits_front(W, u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge, u.ge_adv,
-                                   u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0,
-                                   vb_scale, sgb.dcond + (size_t)i * vits.upc, L.st, nullptr, u.speed);
+                    r = vits_front(W, u, vb_scale, sgb.dcond + (size_t)i * vits.upc, L.st);
                 }
                 if (!r)
                     hipMemcpy2DAsync(sgb.z + sgb.h_off[i], (size_t)sgb.T * 4, W.z, (size_t)sgb.h_len[i] * 4,
                                      (size_t)sgb.h_len[i] * 4, 192, hipMemcpyDeviceToDevice, L.st);
             } else {
-                r = vits_decode_pass(L.ws, u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge,
-                                     u.ge_adv, u.noise_mode == 1 ? u.eps : nullptr,
-                                     u.noise_mode == 2 ? u.noise_seed : 0, vb_scale, u.audio, L.st,
-                                     use_convh ? vflags + i : nullptr, false, u.speed);
+                r = vits_decode_pass(L.ws, u, vb_scale, L.st, use_convh ? vflags + i : nullptr, false);
             }
             if (r) {
                 vb_rcs[l] = r;
@@ -1607,12 +1581,7 @@ int gsv_engine::vits_batch_finish(hipStream_t s) {
         for (int i = 0; i < n; ++i) {
             if (!vflags_host[i]) continue;
             ++vits_f32_reruns;
-            const gsv_vits_item& u = vb_items[i];
-            if (int r = vits_decode_pass(vws, u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge,
-                                         u.ge_adv, u.noise_mode == 1 ? u.eps : nullptr,
-                                         u.noise_mode == 2 ? u.noise_seed : 0, vb_scale, u.audio, s, nullptr,
-                                         false, u.speed))
-                return r;
+            if (int r = vits_decode_pass(vws, vb_items[i], vb_scale, s, nullptr, false)) return r;
         }
     }
     if (timing) {
@@ -1622,7 +1591,7 @@ int gsv_engine::vits_batch_finish(hipStream_t s) {
     }
     if (hipGetLastError() != hipSuccess) return set_error(GSV_E_HIP, "vocoder batch");
     // the output stage: one launch over the batch's items, behind the re-runs, so from the final audio
-    return audio_out_items(vb_items.data(), vb_norm.empty() ? nullptr : vb_norm.data(), n, AO_BATCH_AT, s);
+    return audio_out_items(vb_items.data(), vb_spec.empty() ? nullptr : vb_spec.data(), n, AO_BATCH_AT, s);
 }
 
 // V2: the reference encoder alone (vits(v2)#79-271: ref spectrogram -> MelStyleEncoder ->
@@ -1677,8 +1646,11 @@ extern "C" int gsv_vits_decode(gsv_engine* eng, const int64_t* text_seq, int32_t
     hipSetDevice(eng->device);
     if (!eng->finalized) return set_error(GSV_E_STATE, "weights not finalized");
     StreamScope sc(eng, stream);
-    return eng->vits_decode(text_seq, n_text, sem, n_sem, ref_audio, n_audio, ge, ge_adv, eps, 0,
-                            noise_scale, audio, sc.st());
+    gsv_vits_item u{};   // eps if given, else no noise; no resample, no output stage
+    u.text_seq = text_seq; u.n_text = n_text; u.sem = sem; u.n_sem = n_sem;
+    u.ref_audio = ref_audio; u.n_audio = n_audio; u.ge = ge; u.ge_adv = ge_adv;
+    u.eps = eps; u.noise_mode = eps ? 1 : 0; u.audio = audio;
+    return eng->vits_decode(u, noise_scale, sc.st());
 }
 
 // An item the vocoder entries accept: its noise source, output buffer and speech rate.
@@ -1690,21 +1662,17 @@ static bool vits_item_ok(const gsv_vits_item& u) {
 
 extern "C" int gsv_vits_frames(int32_t n_sem, float speed) { return vits_frames(n_sem, speed); }
 
-// The specs beside items: each valid, and an item with a target, a trim or a pause has `out`.
-static int vits_norm_ok(const gsv_vits_item* items, const gsv_join* norm, int n) {
-    for (int i = 0; norm && i < n; ++i) {
-        if (int r = check_loudness(gsv_loudness{norm[i].target, norm[i].peak, norm[i].stats})) return r;
-        if (norm[i].target != 0.f && !items[i].out)
-            return set_error(GSV_E_ARG, "loudness target on an item without `out`");
-        if (int r = check_join(norm[i])) return r;
-        if (join_active(norm[i]) && !items[i].out) return set_error(GSV_E_ARG, "pause or trim on an item without `out`");
-    }
+// The specs beside items: each valid, and an item with a target, a trim or a pause has `out`
+// (n_in 0: the pass's frame cap, VITS_MAXT_OUT, keeps every item within 640 * 4096 samples).
+static int vits_specs_ok(const gsv_vits_item* items, const gsv_join* spec, int n) {
+    for (int i = 0; spec && i < n; ++i)
+        if (int r = check_spec(spec[i], items[i].out != nullptr, 0)) return r;
     return 0;
 }
 
 // What the four vocoder entries check before anything runs.  one: a single item, checked before
 // the engine's state; else a batch of at least min_n, checked after it, its errors naming the item.
-static int vits_entry_ok(gsv_engine* eng, const gsv_vits_item* items, const gsv_join* norm, int n, bool one,
+static int vits_entry_ok(gsv_engine* eng, const gsv_vits_item* items, const gsv_join* spec, int n, bool one,
                          int min_n = 0) {
     if (!eng) return set_error(GSV_E_ARG, "null engine");
     auto args = [&]() -> int {
@@ -1712,7 +1680,7 @@ static int vits_entry_ok(gsv_engine* eng, const gsv_vits_item* items, const gsv_
         for (int i = 0; i < n; ++i)
             if (!vits_item_ok(items[i]))
                 return set_error(GSV_E_ARG, one ? "bad vocoder item" : "bad vocoder item " + std::to_string(i));
-        return vits_norm_ok(items, norm, n);
+        return vits_specs_ok(items, spec, n);
     };
     if (!one && (n < min_n || (n > 0 && !items))) return set_error(GSV_E_ARG, "bad args");
     if (one)
@@ -1733,12 +1701,8 @@ extern "C" int gsv_vits_decode_item_join(gsv_engine* eng, const gsv_vits_item* i
                                          float noise_scale, void* stream) {
     if (int r = vits_entry_ok(eng, item, join, 1, true)) return r;
     StreamScope sc(eng, stream);
-    const gsv_vits_item& u = *item;
-    if (int r = eng->vits_decode(u.text_seq, u.n_text, u.sem, u.n_sem, u.ref_audio, u.n_audio, u.ge, u.ge_adv,
-                                 u.noise_mode == 1 ? u.eps : nullptr, u.noise_mode == 2 ? u.noise_seed : 0,
-                                 noise_scale, u.audio, sc.st(), u.speed))
-        return r;
-    return eng->audio_out_items(&u, join, 1, gsv_engine::AO_SYNC, sc.st());
+    if (int r = eng->vits_decode(*item, noise_scale, sc.st())) return r;
+    return eng->audio_out_items(item, join, 1, gsv_engine::AO_SYNC, sc.st());
 }
 
 extern "C" int gsv_vits_decode_item_norm(gsv_engine* eng, const gsv_vits_item* item, const gsv_loudness* norm,
@@ -1797,7 +1761,7 @@ extern "C" int gsv_vits_decode_batch_async_join(gsv_engine* eng, int32_t n, cons
     if (int r = eng->vits_batch_finish(nullptr)) return r;
     if (int r = eng->vits_wait(nullptr)) return r;
     eng->vb_items.assign(items, items + n);
-    eng->vb_norm.assign(join, join ? join + n : join);
+    eng->vb_spec.assign(join, join ? join + n : join);
     // ordered after the caller's stream only: the engine stream stays free for the T2S
     // of the next batch, which runs beside this one
     return eng->vits_batch_launch(noise_scale, (hipStream_t)stream, false);

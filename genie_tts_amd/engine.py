@@ -12,7 +12,7 @@ import math
 import os
 import threading
 import weakref
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -96,6 +96,29 @@ class Join(ctypes.Structure):
     and the device span record int32[4] {begin, end, n_speech, n_out} (0: not wanted)."""
     _fields_ = [("target", ctypes.c_float), ("peak", ctypes.c_float), ("stats", ctypes.c_void_p),
                 ("trim", ctypes.c_float), ("pause", ctypes.c_float), ("span", ctypes.c_void_p)]
+
+
+class VocoderCall(NamedTuple):
+    """One vocoder call as its C entry takes it, and what it will have written (Engine._vocoder_call).
+    Holding it keeps every device buffer of the call alive."""
+    items: Any            # the VitsItem array (None: the output stage alone, Engine.audio_convert)
+    specs: Any            # the Join array beside it, or None (NULL): no item has a target, a pause or a trim
+    keep: list            # the input tensors the items point at
+    outs: list            # the result tensor of each item (its `out`, else its 32 kHz audio)
+    a32: list             # the 32 kHz float32 tensor of each item
+    stats: list           # the loudness stats of each item (device float32 [4]; None: no target)
+    spans: list           # the span record of each item (device int32 [4]; None: no trim), rows of ...
+    span_all: Any         # ... this one tensor [trimming items, 4] (None: no item trims)
+
+    def joined(self, outs: Sequence) -> list:
+        """outs (the call's results, after its wait) cut to their joined lengths: for an item with
+        `trim`, out[:n_out] of its span record -- all the records of the call in one device-to-host
+        copy; every other item as it is (with `pause` alone the length is known on the host and
+        nothing is read back)."""
+        if self.span_all is None:
+            return list(outs)
+        n_out = iter(self.span_all.cpu()[:, 3].tolist())
+        return [o if sp is None else o[:next(n_out)] for o, sp in zip(outs, self.spans)]
 
 
 class Sampler(ctypes.Structure):
@@ -1162,61 +1185,42 @@ class Engine:
                     peak=peak, pause=pause, trim=trim)
         if noise_seed is not None and eps is None:
             return self.vits_decode_batch([dict(item, noise_seed=noise_seed)], noise_scale)[0]
-        norm, join = [], []
-        it, keep, audio = self._vits_item(dict(item, eps=eps), norm, join)
-        ld, stats = norm[0]
-        jn = self._join_specs(norm, join)
-        if jn is not None:
-            _check(lib().gsv_vits_decode_item_join(self.h, ctypes.byref(it), jn, ctypes.c_float(noise_scale),
-                                                   _stream()), "gsv_vits_decode_item_join")
-        else:
-            _check(lib().gsv_vits_decode_item_norm(self.h, ctypes.byref(it),
-                                                   None if stats is None else ctypes.byref(ld),
-                                                   ctypes.c_float(noise_scale), _stream()), "gsv_vits_decode_item_norm")
-        self.vits_audio_32k = [keep[-1] if it.out else audio]
-        self.vits_loudness = [stats]
-        return self.vits_joined([audio])[0]
+        call = self._vocoder_call([dict(item, eps=eps)])
+        _check(lib().gsv_vits_decode_item_join(self.h, call.items, call.specs, ctypes.c_float(noise_scale), _stream()),
+               "gsv_vits_decode_item_join")
+        return self._vits_store(call).joined(call.outs)[0]
 
     def audio_convert(self, audio, sample_rate: int = 32000, pcm16: bool = False, loudness: Optional[float] = None,
                       peak: Optional[float] = None, pause: Optional[float] = None, trim: Optional[float] = None):
-        """The output stage alone (gsv_audio_convert): 32 kHz float32 audio [n] -> its
+        """The output stage alone (gsv_audio_join, whose NULL spec is gsv_audio_convert and which the
+        target-only entry forwards to): 32 kHz float32 audio [n] -> its
         audio_samples(n, sample_rate) samples at sample_rate (one of SAMPLE_RATES; the polyphase
         resample of include/genie_engine.h, scipy.signal.resample_poly's default filter), as float32
         or, with pcm16, saturated int16 ((x * 32767).astype(int16), the reference's chunk format).
         One launch on the GPU; a device tensor.
-        loudness / peak (gsv_audio_normalize): the audio is first measured by ITU-R BS.1770-4 and
+        loudness / peak: the audio is first measured by ITU-R BS.1770-4 and
         every sample multiplied, before the int16 conversion, by the gain that brings it to
         `loudness` LUFS, limited so that the 32 kHz sample peak stays under `peak` (linear, None:
         -1 dBFS); self.vits_loudness[0] is then the device stats [loudness, peak, gain, blocks_kept].
-        pause / trim (gsv_audio_join; see vocoder_options): only the span of the audio above `trim`
+        pause / trim (see vocoder_options): only the span of the audio above `trim`
         dBFS is converted and `pause` seconds of zeros follow it; self.vits_spans[0] is then the
-        device span record [begin, end, n_speech, n_out] and the result has n_out samples."""
+        device span record [begin, end, n_speech, n_out] and the result has n_out samples; the
+        conversion is then what vits_joined describes (vits_audio_32k stays the last vocoder call's)."""
         t = self.torch
         a = self._dev(audio, t.float32).reshape(-1)
-        ld = check_loudness(loudness, peak)
-        jn = check_join(pause, trim)
-        if jn:
-            ps = jn.get("pause", 0.0)
-            out = t.empty((join_samples(a.numel(), sample_rate, ps),), dtype=t.int16 if pcm16 else t.float32,
-                          device=self.dev)
-            stats = t.empty((4,), dtype=t.float32, device=self.dev) if ld else None
-            spec = self._join_specs([(Loudness(ld["loudness"], ld.get("peak", 0.0), stats.data_ptr()) if ld
-                                      else Loudness(), stats)], [jn])
-            _check(lib().gsv_audio_join(self.h, _ptr(a), a.numel(), spec, int(sample_rate), int(bool(pcm16)),
-                                        _ptr(out), _stream()), "gsv_audio_join")
-            self.vits_loudness = [stats]
-            return self.vits_joined([out])[0]
-        out = t.empty((audio_samples(a.numel(), sample_rate),), dtype=t.int16 if pcm16 else t.float32, device=self.dev)
-        if ld:
-            stats = t.empty((4,), dtype=t.float32, device=self.dev)
-            _check(lib().gsv_audio_normalize(self.h, _ptr(a), a.numel(), ctypes.c_float(ld["loudness"]),
-                                             ctypes.c_float(ld.get("peak", 0.0)), int(sample_rate), int(bool(pcm16)),
-                                             _ptr(out), _ptr(stats), _stream()), "gsv_audio_normalize")
-            self.vits_loudness = [stats]
+        opts = check_loudness(loudness, peak)
+        opts.update(check_join(pause, trim))
+        n_out = (join_samples(a.numel(), sample_rate, opts.get("pause", 0.0)) if "pause" in opts or "trim" in opts
+                 else audio_samples(a.numel(), sample_rate))
+        out = t.empty((n_out,), dtype=t.int16 if pcm16 else t.float32, device=self.dev)
+        call = self._vocoder_specs([opts], keep=[a], outs=[out], a32=self.vits_audio_32k)
+        _check(lib().gsv_audio_join(self.h, _ptr(a), a.numel(), call.specs, int(sample_rate), int(bool(pcm16)),
+                                    _ptr(out), _stream()), "gsv_audio_join")
+        if call.span_all is None and "pause" not in opts:   # no join option: the last call stays, but for the stats
+            if call.specs is not None:
+                self.vits_loudness = call.stats
             return out
-        _check(lib().gsv_audio_convert(self.h, _ptr(a), a.numel(), int(sample_rate), int(bool(pcm16)), _ptr(out),
-                                       _stream()), "gsv_audio_convert")
-        return out
+        return self._vits_store(call).joined(call.outs)[0]
 
     def audio_loudness(self, audio):
         """(loudness in LUFS, sample peak) of 32 kHz float32 audio [n], n <= 640 * 4096, by ITU-R
@@ -1252,92 +1256,98 @@ class Engine:
     vits_audio_32k: list = []      # the 32 kHz float32 tensors of the last vocoder call, in item order
     vits_loudness: list = []       # its items' loudness stats (device float32 [4]; None: not normalised)
     vits_spans: list = []          # its items' span records (device int32 [4]; None: not trimmed)
-    _vits_span_all = None          # the one tensor [items, 4] they are rows of
+    _vits_call = None              # the last call itself (VocoderCall), which the three above are read from
+    _vits_async_call = None        # the overlapped single call in flight (held until vits_wait)
+    _vits_batch_calls = None       # the overlapped batch in flight and the one before it (until vits_batch_wait)
 
-    def _join_specs(self, norm: list, join: list):
-        """The gsv_join array of a call from its items' (Loudness, stats) and join options (the
-        lists _vits_item fills), or None when no item has a pause or a trim: the call is then the
-        `_norm` one.  The span records of the items that trim are rows of one device tensor, so
-        vits_joined reads them in a single copy."""
-        t = self.torch
-        self.vits_spans, self._vits_span_all = [None] * len(join), None
-        if not any(join):
-            return None
-        rows = [i for i, j in enumerate(join) if "trim" in j]
-        if rows:
-            self._vits_span_all = t.empty((len(rows), 4), dtype=t.int32, device=self.dev)
-            for r, i in enumerate(rows):
-                self.vits_spans[i] = self._vits_span_all[r]
-        arr = (Join * len(join))()
-        for i, ((ld, _), j) in enumerate(zip(norm, join)):
-            sp = self.vits_spans[i]
-            arr[i] = Join(ld.target, ld.peak, ld.stats, j.get("trim", 0.0), j.get("pause", 0.0),
-                          0 if sp is None else sp.data_ptr())
-        return arr
+    def _vits_store(self, call: VocoderCall) -> VocoderCall:
+        """Make `call` the last vocoder call: vits_joined and the three lists above describe it."""
+        self._vits_call = call
+        self.vits_audio_32k, self.vits_loudness, self.vits_spans = call.a32, call.stats, call.spans
+        return call
 
     def vits_joined(self, outs: Sequence):
-        """The results of the last vocoder call (after its wait) cut to their joined lengths: for an
-        item with `trim`, out[:n_out] of its span record -- all the records of the call in one
-        device-to-host copy; every other item as it is (with `pause` alone the length is known on
-        the host and nothing is read back)."""
-        if self._vits_span_all is None:
-            return list(outs)
-        rec = self._vits_span_all.cpu()
-        r, res = 0, []
-        for o, sp in zip(outs, self.vits_spans):
-            if sp is None:
-                res.append(o)
-            else:
-                res.append(o[:int(rec[r, 3])])
-                r += 1
-        return res
+        """The results of the last vocoder call (after its wait) cut to their joined lengths
+        (VocoderCall.joined)."""
+        return list(outs) if self._vits_call is None else self._vits_call.joined(outs)
 
-    def _vits_item(self, it: dict, norm: Optional[list] = None, join: Optional[list] = None):
-        """(VitsItem, tensors it points at, result tensor) of one vocoder call, its option keys
-        resolved by vocoder_options.  With sample_rate / pcm16 / loudness the result is the output
-        stage's tensor (the item's `out`), and the 32 kHz float32 audio, still written, is the last
-        of the kept tensors.  norm: a list that receives the item's (Loudness, stats tensor or None);
-        join: one that receives its pause / trim options (empty: none)."""
-        opts = vocoder_options(*(it.get(k) for k in VOCODER_OPTIONS))
+    def _vocoder_specs(self, opts: Sequence[dict], keep: list, outs: list, a32: list, items=None) -> VocoderCall:
+        """The VocoderCall of buffers already made, from their resolved options (vocoder_options):
+        the gsv_join array beside them -- None (NULL: the plain call) when no item has a loudness
+        target, a pause or a trim, else one entry per item, all zero for an item without options.
+        The stats of the items with a target are device float32 [4] tensors; the span records of
+        the items that trim are rows of one device int32 tensor, so joined() reads them in a single
+        copy."""
         t = self.torch
-        ts, sem = self._ids(it["text_seq"]), self._ids(it["pred_semantic"])
-        G = sem.numel()
-        ra = it.get("ref_audio")
-        ra = None if ra is None else self._dev(ra, t.float32).reshape(-1)
-        g = it.get("ge")
-        g = None if g is None else self._dev(g, t.float32).reshape(-1)
-        ga = it.get("ge_advanced")
-        ga = None if ga is None else self._dev(ga, t.float32).reshape(-1)
-        speed = opts.get("speed", 1.0)
-        frames = vits_frames(G, speed)
-        e = it.get("eps")
-        e = None if e is None else self._dev(e, t.float32).reshape(192, frames)
-        seed = it.get("noise_seed")
-        mode = 1 if e is not None else (2 if seed is not None else 0)
-        audio = t.empty((640 * frames,), dtype=t.float32, device=self.dev)
-        item = VitsItem(ts.data_ptr(), ts.numel(), sem.data_ptr(), G, 0 if ra is None else ra.data_ptr(),
-                        0 if ra is None else ra.numel(), 0 if g is None else g.data_ptr(),
-                        0 if ga is None else ga.data_ptr(), 0 if e is None else e.data_ptr(),
-                        int(seed or 0) & 0xFFFFFFFFFFFFFFFF, mode, audio.data_ptr(), speed)
-        target = opts.get("loudness")
-        stats = None if target is None else t.empty((4,), dtype=t.float32, device=self.dev)
-        if norm is not None:
-            norm.append((Loudness() if target is None else Loudness(target, opts.get("peak", 0.0), stats.data_ptr()),
-                         stats))
-        elif target is not None:
-            raise EngineError("loudness on an entry without a loudness spec")
-        jn = {k: opts[k] for k in ("pause", "trim") if k in opts}
-        if join is not None:
-            join.append(jn)
-        elif jn:
-            raise EngineError("pause / trim on an entry without a join spec")
-        if opts.keys() <= {"speed"}:
-            return item, [ts, sem, ra, g, ga, e], audio
-        rate, pcm = opts.get("sample_rate", 32000), "pcm16" in opts
-        n_out = join_samples(640 * frames, rate, jn.get("pause", 0.0)) if jn else audio_samples(640 * frames, rate)
-        out = t.empty((n_out,), dtype=t.int16 if pcm else t.float32, device=self.dev)
-        item.out_rate, item.out_format, item.out = rate, int(pcm), out.data_ptr()
-        return item, [ts, sem, ra, g, ga, e, audio], out
+        stats, spans, span_all = [None] * len(opts), [None] * len(opts), None
+        if not any("loudness" in o or "pause" in o or "trim" in o for o in opts):
+            return VocoderCall(items, None, keep, outs, a32, stats, spans, None)
+        rows = [i for i, o in enumerate(opts) if "trim" in o]
+        if rows:
+            span_all = t.empty((len(rows), 4), dtype=t.int32, device=self.dev)
+            for r, i in enumerate(rows):
+                spans[i] = span_all[r]
+        specs = (Join * len(opts))()
+        for i, (j, o) in enumerate(zip(specs, opts)):
+            if "loudness" in o:
+                stats[i] = t.empty((4,), dtype=t.float32, device=self.dev)
+                j.target, j.peak, j.stats = o["loudness"], o.get("peak", 0.0), stats[i].data_ptr()
+            if "pause" in o:
+                j.pause = o["pause"]
+            if "trim" in o:
+                j.trim, j.span = o["trim"], spans[i].data_ptr()
+        return VocoderCall(items, specs, keep, outs, a32, stats, spans, span_all)
+
+    def _vocoder_call(self, items: Sequence[dict]) -> VocoderCall:
+        """One vocoder call over item dicts (text_seq, pred_semantic, ref_audio or ge + ge_advanced,
+        optional eps or noise_seed, and the option keys of vocoder_options, resolved here): the
+        VitsItem array, its gsv_join array (_vocoder_specs) and every tensor they point at.  With
+        sample_rate / pcm16 / loudness / pause / trim an item's result is the output stage's tensor
+        (its `out`); the 32 kHz float32 audio is written as well."""
+        t = self.torch
+        arr = (VitsItem * len(items))()
+        all_opts, keep, outs, a32 = [], [], [], []
+        for i, it in enumerate(items):
+            opts = vocoder_options(*(it.get(k) for k in VOCODER_OPTIONS))
+            ts, sem = self._ids(it["text_seq"]), self._ids(it["pred_semantic"])
+            G = sem.numel()
+            ra, g, ga = it.get("ref_audio"), it.get("ge"), it.get("ge_advanced")
+            ra = None if ra is None else self._dev(ra, t.float32).reshape(-1)
+            g = None if g is None else self._dev(g, t.float32).reshape(-1)
+            ga = None if ga is None else self._dev(ga, t.float32).reshape(-1)
+            speed = opts.get("speed", 1.0)
+            frames = vits_frames(G, speed)
+            e = it.get("eps")
+            e = None if e is None else self._dev(e, t.float32).reshape(192, frames)
+            seed = it.get("noise_seed")
+            mode = 1 if e is not None else (2 if seed is not None else 0)
+            audio = t.empty((640 * frames,), dtype=t.float32, device=self.dev)
+            item = VitsItem(ts.data_ptr(), ts.numel(), sem.data_ptr(), G, 0 if ra is None else ra.data_ptr(),
+                            0 if ra is None else ra.numel(), 0 if g is None else g.data_ptr(),
+                            0 if ga is None else ga.data_ptr(), 0 if e is None else e.data_ptr(),
+                            int(seed or 0) & 0xFFFFFFFFFFFFFFFF, mode, audio.data_ptr(), speed)
+            out = audio
+            if not opts.keys() <= {"speed"}:
+                rate, pcm = opts.get("sample_rate", 32000), "pcm16" in opts
+                n_out = (join_samples(640 * frames, rate, opts.get("pause", 0.0)) if "pause" in opts or "trim" in opts
+                         else audio_samples(640 * frames, rate))
+                out = t.empty((n_out,), dtype=t.int16 if pcm else t.float32, device=self.dev)
+                item.out_rate, item.out_format, item.out = rate, int(pcm), out.data_ptr()
+            arr[i] = item
+            all_opts.append(opts)
+            keep += [ts, sem, ra, g, ga, e]
+            outs.append(out)
+            a32.append(audio)
+        return self._vocoder_specs(all_opts, keep, outs, a32, arr)
+
+    def _vits_item(self, it: dict):
+        """(VitsItem, what keeps its tensors alive, result tensor) of one item dict, for a direct call
+        of a plain C entry: a _vocoder_call of it alone (the call itself is the keeper).  An item with
+        a loudness target, a pause or a trim has no plain form: EngineError."""
+        call = self._vocoder_call([it])
+        if call.specs is not None:
+            raise EngineError("loudness / pause / trim need the spec beside the item: use _vocoder_call")
+        return call.items[0], call, call.outs[0]
 
     @staticmethod
     def vits_frames(n_sem: int, speed: float = 1.0) -> int:
@@ -1350,60 +1360,30 @@ class Engine:
         noise_seed, and the option keys of vocoder_options.  Returns one audio tensor [640 T'] per
         item (1280 G at speed 1), the output stage's where the item asks for it (one stage launch
         for the batch); self.vits_audio_32k then holds every item's 32 kHz audio."""
-        arr, norm, keep, outs, a32 = self._vits_items(items)
-        if isinstance(norm, ctypes.Array) and norm._type_ is Join:
-            _check(lib().gsv_vits_decode_batch_join(self.h, len(items), arr, norm, ctypes.c_float(noise_scale),
-                                                    _stream()), "gsv_vits_decode_batch_join")
-        else:
-            _check(lib().gsv_vits_decode_batch_norm(self.h, len(items), arr, norm, ctypes.c_float(noise_scale),
-                                                    _stream()), "gsv_vits_decode_batch_norm")
-        self.vits_audio_32k = a32
-        return self.vits_joined(outs)
-
-    def _vits_items(self, items: Sequence[dict]):
-        """The item array of a batch, its gsv_loudness array (None when no item has a target; a
-        gsv_join array when an item has a pause or a trim), the kept tensors, the results and the
-        32 kHz tensors."""
-        arr = (VitsItem * len(items))()
-        keep, outs, a32, norm, join = [], [], [], [], []
-        for i, it in enumerate(items):
-            arr[i], k, audio = self._vits_item(it, norm, join)
-            keep += k
-            outs.append(audio)
-            a32.append(k[-1] if arr[i].out else audio)
-        self.vits_loudness = [st for _, st in norm]
-        jn = self._join_specs(norm, join)
-        if jn is not None:
-            return arr, jn, keep + self.vits_loudness + [self._vits_span_all], outs, a32
-        if not any(st is not None for st in self.vits_loudness):
-            return arr, None, keep, outs, a32
-        keep += self.vits_loudness
-        return arr, (Loudness * len(items))(*[l for l, _ in norm]), keep, outs, a32
+        call = self._vocoder_call(items)
+        _check(lib().gsv_vits_decode_batch_join(self.h, len(items), call.items, call.specs, ctypes.c_float(noise_scale),
+                                                _stream()), "gsv_vits_decode_batch_join")
+        return self._vits_store(call).joined(call.outs)
 
     def vits_decode_batch_async(self, items: Sequence[dict], noise_scale: float = 0.5):
         """vits_decode_batch without the join (gsv_vits_decode_batch_async): the lanes run
         beside whatever T2S is issued next.  Returns the audio tensors, valid after
         vits_batch_wait(); with `trim`, vits_joined(them) then cuts them to their joined lengths."""
-        arr, norm, keep, outs, a32 = self._vits_items(items)
-        if isinstance(norm, ctypes.Array) and norm._type_ is Join:
-            _check(lib().gsv_vits_decode_batch_async_join(self.h, len(items), arr, norm, ctypes.c_float(noise_scale),
-                                                          _stream()), "gsv_vits_decode_batch_async_join")
-        else:
-            _check(lib().gsv_vits_decode_batch_async_norm(self.h, len(items), arr, norm,
-                                                          ctypes.c_float(noise_scale), _stream()),
-                   "gsv_vits_decode_batch_async_norm")
-        self.vits_audio_32k = a32
+        call = self._vocoder_call(items)
+        _check(lib().gsv_vits_decode_batch_async_join(self.h, len(items), call.items, call.specs,
+                                                      ctypes.c_float(noise_scale), _stream()),
+               "gsv_vits_decode_batch_async_join")
         # items and device buffers live until the wait -- also a previous batch's, which this
         # call only ordered behind the engine stream (its lanes may still read them)
         # (one generation back: a batch older than the previous one was joined by this launch)
-        prev = getattr(self, "_vits_batch_keep", None)
-        self._vits_batch_keep = (arr, keep, outs, prev[:3] if prev else None)
-        return outs
+        prev = self._vits_batch_calls
+        self._vits_batch_calls = (self._vits_store(call), prev and prev[0])
+        return call.outs
 
     def vits_batch_wait(self):
         """Finish the pending vits_decode_batch_async; orders the current stream after it."""
         _check(lib().gsv_vits_batch_wait(self.h, _stream()), "gsv_vits_batch_wait")
-        self._vits_batch_keep = None
+        self._vits_batch_calls = None
 
     vocoder_cus = 0
 
@@ -1415,27 +1395,16 @@ class Engine:
     def vits_decode_async(self, item: dict, noise_scale: float = 0.5):
         """Start one vocoder call on the vocoder CUs (gsv_vits_decode_async) and return its
         audio tensor [640 T'], valid after vits_wait().  item as for vits_decode_batch."""
-        norm, join = [], []
-        it, keep, audio = self._vits_item(item, norm, join)
-        ld, stats = norm[0]
-        jn = self._join_specs(norm, join)
-        if jn is not None:
-            _check(lib().gsv_vits_decode_async_join(self.h, ctypes.byref(it), jn, ctypes.c_float(noise_scale),
-                                                    _stream()), "gsv_vits_decode_async_join")
-        else:
-            _check(lib().gsv_vits_decode_async_norm(self.h, ctypes.byref(it),
-                                                    None if stats is None else ctypes.byref(ld),
-                                                    ctypes.c_float(noise_scale), _stream()),
-                   "gsv_vits_decode_async_norm")
-        self._vits_keep = keep + [stats, self._vits_span_all]   # device inputs stay alive until the call is finished
-        self.vits_loudness = [stats]
-        self.vits_audio_32k = [keep[-1] if it.out else audio]
-        return audio
+        call = self._vocoder_call([item])
+        _check(lib().gsv_vits_decode_async_join(self.h, call.items, call.specs, ctypes.c_float(noise_scale), _stream()),
+               "gsv_vits_decode_async_join")
+        self._vits_async_call = self._vits_store(call)   # device inputs stay alive until the call is finished
+        return call.outs[0]
 
     def vits_wait(self):
         """Finish the pending vits_decode_async call; orders the current stream after it."""
         _check(lib().gsv_vits_wait(self.h, _stream()), "gsv_vits_wait")
-        self._vits_keep = None
+        self._vits_async_call = None
 
     def ref_encode(self, ref_audio):
         """V2: the vocoder's reference branch alone (gsv_ref_encode) -> ge [512] on the device;

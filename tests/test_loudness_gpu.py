@@ -225,9 +225,9 @@ def test_bad_arguments_are_refused_before_any_launch():
         with pytest.raises(ValueError):
             e.audio_convert(x, 48000, loudness=-16.0, peak=v)
     txt, sem = _utt(8, 10)
-    norm = []
-    item, keep, res = e._vits_item(dict(text_seq=txt, pred_semantic=sem, loudness=-16.0, **_cond("v2")), norm)
-    ld = norm[0][0]
+    call = e._vocoder_call([dict(text_seq=txt, pred_semantic=sem, loudness=-16.0, **_cond("v2"))])
+    item, spec = call.items[0], call.specs[0]
+    ld = Loudness(spec.target, spec.peak, spec.stats)                # the `_norm` entries' form of the item's spec
     assert item.out and ld.target == -16.0
     entries = (lambda: L.gsv_vits_decode_item_norm(e.h, ctypes.byref(item), ctypes.byref(ld), f(0.5), _stream()),
                lambda: L.gsv_vits_decode_batch_norm(e.h, 1, ctypes.byref(item), ctypes.byref(ld), f(0.5), _stream()),
@@ -354,7 +354,7 @@ def test_fp16_range_rerun_measures_the_reruns_audio(setup):
 
 
 def test_methods_without_a_target_give_the_plain_entries_bits(setup):
-    """The Engine's vocoder methods call the `_norm` entries whether or not an item has a target.
+    """The Engine's vocoder methods call the `_join` entries whether or not an item has a target.
     Without one, each returns the bits of a direct call of the plain C entry on the same item
     (G = 8, 3 text ids, Philox noise from one seed), as float32 at 32 kHz and as int16 at 16 kHz.
     vits_decode takes the batch entry with a seed and the item entry without one (zero noise)."""

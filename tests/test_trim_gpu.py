@@ -228,9 +228,9 @@ def test_bad_values_are_refused_before_any_launch():
         j = Join(0.0, 0.0, None, trim, pause, None)
         assert lib().gsv_audio_join(e.h, p(x), 640, ctypes.byref(j), 32000, 0, p(out), _stream()) == -1
     txt, sem = _utt(8, 10)
-    norm, join = [], []
-    item, keep, res = e._vits_item(dict(text_seq=txt, pred_semantic=sem, pause=0.3, **_cond("v2")), norm, join)
-    assert join == [dict(pause=0.3)] and res.shape == (640 * 16 + 9600,)
+    vc = e._vocoder_call([dict(text_seq=txt, pred_semantic=sem, pause=0.3, **_cond("v2"))])   # (keeps the item's tensors)
+    item, res = vc.items[0], vc.outs[0]
+    assert (vc.specs[0].pause, vc.specs[0].trim) == (np.float32(0.3), 0.0) and res.shape == (640 * 16 + 9600,)
     for j in (Join(0.0, 0.0, None, -10.0, 0.0, None), Join(0.0, 0.0, None, 0.0, 9.0, None)):
         for call in (lambda: lib().gsv_vits_decode_item_join(e.h, ctypes.byref(item), ctypes.byref(j),
                                                              ctypes.c_float(0.5), _stream()),
